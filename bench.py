@@ -2,7 +2,13 @@
 """Headline benchmark: device-resident GB/s of the 20-client wide_resnet16_8
 parameter reduction (BASELINE.json metric, configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the one
+JSON line with the headline; ``--dump-outputs DIR`` also writes the global
+state the last timed step produced as ``DIR/<name>.npy`` (dump_outputs).
+Everything else this file measures or checks (see the last paragraph) runs
+only with ``--full``.
 
 A step is one aggregation of 20 client state_dicts (wide_resnet16_8,
 CIFAR-10 layout: 82 fp32 keys + 16 int64 keys, B = 43,888,744 bytes) into the
@@ -17,11 +23,13 @@ N·20 slots (every round form of feddct_amd/comm.py and dist.py is timed, see
 the fastest form whose result is bit-identical to the single-GPU reduction.
 
 Also reported on the same JSON line: the roofline of the reduce kernel
-(HIP-event launch time vs the 8 TB/s HBM3E peak), the CPU baseline (the
-reference loop restated in torch, oracle/torch_mirror.py, on this host's
-cores; rank 0, N=1 only), parity of the output against the reference's
-committed SHA-256 digest, and the host-inclusive rate (pinned H2D + kernel +
-D2H).
+(HIP-event launch time vs the 8 TB/s HBM3E peak) and, with ``--full`` only
+(each takes runs of its own), this GPU's copy / read / write ceilings, the
+weighted and broadcast variants, the other BASELINE configs, the drop-in
+timings, the CPU baseline (the reference loop restated in torch,
+oracle/torch_mirror.py, on this host's cores; rank 0, N=1 only), parity of
+the output against the reference's committed SHA-256 digest, and the
+host-inclusive rate (pinned H2D + kernel + D2H).
 """
 from __future__ import annotations
 
@@ -81,6 +89,16 @@ def timed_launches(fn, steps, warmup, sync_group=None, per_launch=None):
     if per_launch is not None:
         per_launch[:] = [ev[i].elapsed_time(ev[i + 1]) / 1e3 for i in range(steps)]
     return ev[0].elapsed_time(ev[-1]) / 1e3 / steps, wall / steps
+
+
+def preheat(fn, seconds=0.25):
+    """``fn`` launched back to back for a fixed ``seconds`` of wall time: the
+    GPU leaves its idle clocks before the warm-up and the timed steps."""
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(50):
+            fn()
+        torch.cuda.synchronize()
 
 
 def launch_stats(ts):
@@ -223,6 +241,26 @@ def digest_of(layout, out32, out64, prefix=""):
         h.update(s.key[len(prefix):].encode())
         h.update(np.ascontiguousarray(src[s.offset:s.offset + s.numel]).tobytes())
     return h.hexdigest()
+
+
+def dump_outputs(dirname, layout, out32, out64):
+    """--dump-outputs: the global state the timed path left in its output
+    buckets, as a caller reads it — every key's elements in state_dict order
+    (the padding between keys is no tensor's and is left out):
+    ``global_f32.npy`` (float32, the fp32 keys; 43.9 MB on the headline
+    layout) and ``global_i64.npy`` (the int64 counters as float64: exact
+    below 2**53).  The inputs are synthetic with fixed seeds, so two builds
+    run with the same arguments are compared file for file."""
+    os.makedirs(dirname, exist_ok=True)
+    f = out32.cpu().numpy()
+    i = out64.cpu().numpy()
+    own = [s for s in layout.slots if s.alias_of is None]
+    f32 = [f[s.offset:s.offset + s.numel] for s in own if s.kind != "i64"]
+    i64 = [i[s.offset:s.offset + s.numel] for s in own if s.kind == "i64"]
+    np.save(os.path.join(dirname, "global_f32.npy"),
+            np.concatenate(f32 or [f[:0]]).astype(np.float32, copy=False))
+    np.save(os.path.join(dirname, "global_i64.npy"),
+            np.concatenate(i64 or [i[:0]]).astype(np.float64))
 
 
 def ulp_dist(a: torch.Tensor, b: torch.Tensor) -> int:
@@ -1538,7 +1576,7 @@ def multi_gpu(args, world, rank, dev, group, layout, manifest, clients, out32, o
             "note": "not the default; NOT within north_star's 1 ULP"}
     if striped_host is not None:
         extra["exact_mode_host_ingress"] = striped_host
-    if not args.kernel_only:
+    if args.extras:
         log(f"[rank {rank}] config 5 sharded")
         try:
             with phase("config 5 sharded"):
@@ -1546,7 +1584,8 @@ def multi_gpu(args, world, rank, dev, group, layout, manifest, clients, out32, o
                     dev, world, rank, group, max(10, args.steps // 2), ncomm, args.chain_chunks)
         except Exception as e:  # noqa: BLE001
             extra["cfg5_feddct_c100_n24_sharded"] = {"error": repr(e)}
-    return best_t, t_kernel, ncomm
+    return best_t, t_kernel, ncomm, modes[best]["out"]
+
 
 def model_check(report):
     """The cost model against the run: for every mode
@@ -1646,7 +1685,16 @@ def main():
                     help="run the N>1 path (every round form, native RCCL communicator "
                          "included) with however many ranks there are, also one: a "
                          "one-GPU rehearsal of the driver's multi-GPU command")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: ceilings, weighted and "
+                         "broadcast variants, parity, host-inclusive and drop-in timings, the "
+                         "other configs, the CPU baseline (N>1: config 5 sharded)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the global state the last step "
+                         "produced as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    # what --full adds; --kernel-only (profiler runs) never carries it
+    args.extras = args.full and not args.kernel_only
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     multi = world > 1 or args.multi_rehearsal
@@ -1662,7 +1710,7 @@ def main():
     if args.same_device:
         local_rank = 0
     idle_state = None
-    if world == 1 and not args.kernel_only:
+    if world == 1 and args.extras:
         try:
             idle_state = gpu_state_idle()
         except Exception as e:  # noqa: BLE001  (reported, never fatal)
@@ -1695,7 +1743,7 @@ def main():
     ncomm = None
     if not multi:
         per = []
-        if not args.kernel_only:
+        if args.extras:
             # streaming work BEFORE the headline's own W warmups, so the
             # timed steps do not see the clocks ramp: the copy ceiling of this
             # box, the weighted and broadcast variants of the same reduction
@@ -1733,11 +1781,19 @@ def main():
             tw, _ = timed_launches(wred, max(100, args.steps // 2), max(20, args.warmup))
             extra["weighted_GBps"] = round(nbytes_rank / tw / 1e9, 1)
             extra["weighted_us"] = round(tw * 1e6, 2)
+        elif not args.kernel_only:
+            # a plain run has no streaming work before its W warm-ups: the
+            # headline's own launches bring the clocks up instead (set-up; the
+            # same figure read 0.8-2.5 % low when timed from an idle GPU).
+            # Not under --kernel-only: a profiler counts every launch
+            preheat(reducer)
         # the headline straight after the streaming above: no host-side check
         # (digest hashing idles the GPU for ~0.1 s) between them and its W
         # warm-ups
         t_step, wall = timed_launches(reducer, args.steps, args.warmup)
         t_kernel = t_step
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, layout, out32, out64)
         if "read_ceiling_GBps" in extra:
             # this box's own bound: the headline as a fraction of the copy and
             # of the read-only rate measured just before it
@@ -1745,7 +1801,7 @@ def main():
             extra["headline_vs_box_ceilings"] = {
                 "copy": round(gbs / extra["copy_ceiling_GBps"], 4),
                 "read_only": round(gbs / extra["read_ceiling_GBps"], 4)}
-        if not args.kernel_only:
+        if args.extras:
             timed_launches(wred, max(100, args.steps // 2), 20, per_launch=wper)
             extra["weighted_launch"] = launch_stats(wper)
             extra["weighted_parity"] = weighted_digest_check("wrn16_8_c10/n20/sizes_1_20",
@@ -1820,11 +1876,15 @@ def main():
             except Exception as e:  # noqa: BLE001
                 extra["cfg1_host_resident_n2"] = {"error": repr(e)}
     else:
-        t_step, t_kernel, ncomm = multi_gpu(args, world, rank, dev, group, layout, manifest,
-                                            clients, out32, out64, reducer, nbytes_rank, extra)
+        t_step, t_kernel, ncomm, sel_out = multi_gpu(
+            args, world, rank, dev, group, layout, manifest, clients, out32, out64, reducer,
+            nbytes_rank, extra)
+        if args.dump_outputs and rank == 0:
+            # the selected form's result (the parity phase brought it to rank 0)
+            dump_outputs(args.dump_outputs, layout, *sel_out)
 
     line = build_line(args, world, nbytes_rank, layout.state_bytes(), t_step, t_kernel, extra)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.kernel_only:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.extras:
         try:
             line["cpu_baseline"] = run_cpu_baseline(layout, manifest, clients, args.cpu_budget)
         except Exception as e:  # report, never hide

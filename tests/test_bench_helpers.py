@@ -74,6 +74,39 @@ def test_build_line_keeps_the_bench_contract():
     assert line["config"]["algorithmic_bytes_per_step"] == 2 * nb
 
 
+def test_dump_outputs_writes_every_key_in_order(golden, tmp_path):
+    """--dump-outputs: the keys' elements in state_dict order without the
+    padding between them, fp32 keys as float32 and the int64 counters as
+    float64, the same bytes on a second call."""
+    import numpy as np
+    from feddct_amd.layout import BucketLayout
+    lay = BucketLayout.from_manifest(golden["manifest"]["small"])
+    g = torch.Generator().manual_seed(3)
+    o32 = torch.randn(max(64, lay.f32_numel), generator=g)
+    o64 = torch.randint(0, 1 << 40, (max(1, lay.i64_numel),), generator=g)
+    bench.dump_outputs(str(tmp_path / "a"), lay, o32, o64)
+    bench.dump_outputs(str(tmp_path / "b"), lay, o32, o64)
+    assert sorted(os.listdir(tmp_path / "a")) == ["global_f32.npy", "global_i64.npy"]
+    f = np.load(tmp_path / "a" / "global_f32.npy")
+    i = np.load(tmp_path / "a" / "global_i64.npy")
+    assert f.dtype == np.float32 and i.dtype == np.float64
+    own = [s for s in lay.slots if s.alias_of is None]
+    assert f.size == sum(s.numel for s in own if s.kind != "i64")
+    assert i.size == sum(s.numel for s in own if s.kind == "i64")
+    pf = pi = 0
+    for s in own:
+        if s.kind == "i64":
+            want = o64[s.offset:s.offset + s.numel].numpy()
+            assert np.array_equal(i[pi:pi + s.numel].astype(np.int64), want), s.key
+            pi += s.numel
+        else:
+            want = o32[s.offset:s.offset + s.numel].numpy()
+            assert f[pf:pf + s.numel].tobytes() == want.tobytes(), s.key
+            pf += s.numel
+    for name in ("global_f32.npy", "global_i64.npy"):
+        assert (tmp_path / "a" / name).read_bytes() == (tmp_path / "b" / name).read_bytes()
+
+
 def test_parse_smi_reads_clocks_power_and_temperatures():
     """bench.gpu_state_under_load's parser on rocm-smi --json text as the box
     prints it (a warning line first)."""

@@ -1,10 +1,12 @@
 #!/bin/bash
-# The driver's own N=1 bench command (20 steps after 5 warm-up), summarised.
+# The driver's own N=1 bench command (20 steps after 5 warm-up) with --full
+# (the ceilings, the round and the drop-in timings ride on it), summarised.
 set -o pipefail
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
-out=gpurun_out/driver_like_${1:-x}.json
-timeout -k 10 420 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out 2> ${out%.json}.err || exit $?
+cd "$(dirname "$0")/.."
+OUT="${FA_OUT_DIR:-bench_out}"
+mkdir -p "$OUT"
+out=$OUT/driver_like_${1:-x}.json
+timeout -k 10 420 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out 2> ${out%.json}.err || exit $?
 python3 - "$out" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
