@@ -18,8 +18,8 @@
 //   prox_finish   : one workgroup: per tensor the chunk partials in a fixed
 //                   order -> sqrt -> norms[k]; sum of norms -> total
 //                   (deterministic: no atomics);
-//   prox_grad     : d/dw ||w - w_t|| = (w - w_t)/||w - w_t|| (0 where the
-//                   norm is 0, as torch's norm backward), scaled by the
+//   prox_grad     : d/dw ||w - w_t|| = (w - w_t)/||w - w_t|| (0 only where
+//                   the norm is 0, as torch's norm backward), scaled by the
 //                   incoming gradient; the global side gets the negation.
 //
 // HBM-bound: forward reads 2 B per element pair, backward reads 2 and writes
@@ -264,7 +264,9 @@ __global__ __launch_bounds__(kBlk) void prox_grad(const NormChunk* __restrict__ 
                                                   float* __restrict__ ga, float* __restrict__ gb) {
   const NormChunk c = chunks[blockIdx.x];
   const float nk = norms[c.seg];
-  const float g = nk > 0.f ? (*gout) * alpha / nk : 0.f;
+  // only a zero norm is masked (torch's norm backward): a NaN norm gives NaN
+  // gradients for its whole tensor, an infinite one zeros for finite elements
+  const float g = nk == 0.f ? 0.f : (*gout) * alpha / nk;
   const int nv = c.count / 4;
   const f4* pa = reinterpret_cast<const f4*>(a + c.start);
   const f4* pb = reinterpret_cast<const f4*>(b + c.start);

@@ -306,7 +306,9 @@ int fa_norm_plan_destroy(fa_norm_plan *plan);
 /* norms[k] = ||a_k - b_k||_2 (device, nseg floats); *total = sum_k norms[k] */
 int fa_prox_norms(const fa_norm_plan *plan, const float *a, const float *b,
                   float *norms, float *total, void *stream);
-/* grad_a[e] = (*gout) * alpha * (a[e]-b[e]) / norms[k]  (0 where norms[k]==0);
+/* grad_a[e] = (*gout) * alpha * (a[e]-b[e]) / norms[k]  (0 where norms[k]==0,
+ * and only there: a NaN norm gives NaN for its whole segment, an infinite one
+ * 0 for finite elements — torch's norm backward);
  * grad_b (nullable) = -grad_a.  Only elements inside segments are written. */
 int fa_prox_grad(const fa_norm_plan *plan, const float *a, const float *b,
                  const float *norms, const float *gout, float alpha,

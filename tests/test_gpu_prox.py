@@ -131,8 +131,10 @@ def test_prox_chunks_per_workgroup_same_bits(big, cpw):
 
 
 def test_prox_many_chunks():
-    """4,200 chunks (more partials than the finish stages in one load batch):
-    still torch's norms, repeated launches identical."""
+    """4,200 chunks over 8 tensors (more than half of the 8,192 partials the
+    finish stages in one load batch, still one batch; the two-batch case is
+    test_gpu_prox_edges.py's): still torch's norms, repeated launches
+    identical."""
     numel = 4200 * 4096
     cut = np.linspace(0, numel, 9).astype(np.int64) // 64 * 64
     segs = np.stack([cut[:-1], cut[1:] - cut[:-1]], 1)
