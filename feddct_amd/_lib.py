@@ -43,6 +43,12 @@ FA_PLAN_FLAGS_KNOWN = FA_PLAN_GAPS_ARE_PADDING | FA_PLAN_TUNE_BATCH8 | FA_PLAN_T
     | FA_PLAN_TUNE_NO_BALANCE
 FA_ORDER_TORCH_CPU = 0
 FA_ORDER_TORCH_GPU = 1
+# element type of a plan's floating bucket (fa_plan_create_elem)
+FA_ELEM_F32 = 0
+FA_ELEM_F16 = 1
+FA_ELEM_BF16 = 2
+ELEM_OF_DTYPE = {torch.float32: FA_ELEM_F32, torch.float16: FA_ELEM_F16,
+                 torch.bfloat16: FA_ELEM_BF16}
 
 
 EXPORTS = [
@@ -55,6 +61,7 @@ EXPORTS = [
     "fa_read_probe_f32", "fa_write_probe_f32", "fa_tune_prox_store", "fa_tune_prox_cpw", "fa_chain_levels", "fa_reduce_chain", "fa_torch_gpu_config",
     "fa_plan_create_order", "fa_table_bytes", "fa_reduce_tab",
     "fa_plan_balance_host", "fa_plan_launch_shape", "fa_plan_launch_form",
+    "fa_plan_create_elem", "fa_plan_build_host_elem", "fa_plan_elem",
 ]
 
 
@@ -98,6 +105,11 @@ def _load():
         "fa_last_error": (ctypes.c_char_p, []),
         "fa_plan_create": (_I, [_P, _I, _I64, _P, _I, _I64, _I, ctypes.c_uint,
                                 ctypes.POINTER(_P)]),
+        "fa_plan_create_elem": (_I, [_P, _I, _I64, _P, _I, _I64, _I, ctypes.c_uint, _I,
+                                     ctypes.POINTER(_P)]),
+        "fa_plan_elem": (_I, [_P]),
+        "fa_plan_build_host_elem": (_I, [_P, _I, _I64, _P, _I, _I64, _I, ctypes.c_uint, _I, _P, _I,
+                                         ctypes.POINTER(FaPlanInfo)]),
         "fa_plan_destroy": (_I, [_P]),
         "fa_plan_build_host": (_I, [_P, _I, _I64, _P, _I, _I64, _I, ctypes.c_uint, _P, _I,
                                     ctypes.POINTER(FaPlanInfo)]),
@@ -172,19 +184,25 @@ def seg_array(segs: np.ndarray):
 
 
 def build_tiles_host(segs32, f32_numel, segs64=(), i64_numel=0, tile_elems=0,
-                     flags=FA_PLAN_GAPS_ARE_PADDING):
+                     flags=FA_PLAN_GAPS_ARE_PADDING, elem=None):
     """Tile table of a layout, computed by the library on the host (no GPU):
-    returns (info dict, ndarray of (start, count, kind))."""
+    returns (info dict, ndarray of (start, count, kind)).  ``elem``: the
+    floating bucket's element type (FA_ELEM_*; fa_plan_build_host_elem)."""
+    if elem is not None:
+        def build(*args):
+            return lib.fa_plan_build_host_elem(*args[:8], int(elem), *args[8:])
+    else:
+        build = lib.fa_plan_build_host
     a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
     a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
     info = FaPlanInfo()
-    check(lib.fa_plan_build_host(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
-                                 int(tile_elems), flags, None, 0, ctypes.byref(info)),
+    check(build(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
+                int(tile_elems), flags, None, 0, ctypes.byref(info)),
           "fa_plan_build_host")
     cap = info.ntiles
     arr = (FaTileDesc * max(1, cap))()
-    check(lib.fa_plan_build_host(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
-                                 int(tile_elems), flags, arr, cap, ctypes.byref(info)),
+    check(build(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
+                int(tile_elems), flags, arr, cap, ctypes.byref(info)),
           "fa_plan_build_host")
     tiles = np.array([(arr[i].start, arr[i].count, arr[i].kind) for i in range(cap)],
                      np.int64).reshape(-1, 3)
@@ -216,9 +234,21 @@ class Plan:
     from a layout's segments, or from an explicit tile subset (``tiles``)."""
 
     def __init__(self, segs32, f32_numel, segs64=(), i64_numel=0, tile_elems=0,
-                 flags=FA_PLAN_GAPS_ARE_PADDING, tiles=None, order=FA_ORDER_TORCH_CPU, n=0):
+                 flags=FA_PLAN_GAPS_ARE_PADDING, tiles=None, order=FA_ORDER_TORCH_CPU, n=0,
+                 elem=FA_ELEM_F32):
         h = ctypes.c_void_p()
-        if order != FA_ORDER_TORCH_CPU:
+        self.elem = int(elem)
+        if elem != FA_ELEM_F32:
+            # a 16-bit floating bucket: the CPU order from a segment list only
+            if order != FA_ORDER_TORCH_CPU or tiles is not None:
+                raise FedaggError("a 16-bit plan is cut from a layout's segments in torch's "
+                                  "CPU order (no tile subsets, no torch-GPU order)")
+            a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
+            a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
+            check(lib.fa_plan_create_elem(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
+                                          int(tile_elems), flags, int(elem), ctypes.byref(h)),
+                  "fa_plan_create_elem")
+        elif order != FA_ORDER_TORCH_CPU:
             a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
             a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
             check(lib.fa_plan_create_order(a32, n32, int(f32_numel), a64, n64, int(i64_numel),

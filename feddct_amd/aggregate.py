@@ -40,7 +40,7 @@ from array import array
 from . import _lib, slab
 from . import arena as _arena
 from .arena import ModuleArena, get_arena
-from .layout import BucketLayout
+from .layout import BucketLayout, native16_dtype
 
 __all__ = ["server_aggregate", "server_aggregate_split", "aggregate_weighted", "client_weights",
            "Engine", "engine", "set_summation_order", "summation_order"]
@@ -234,7 +234,7 @@ class Engine:
         if p is None:
             with torch.cuda.device(device):
                 p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
-                              layout.i64_numel)
+                              layout.i64_numel, elem=_lib.ELEM_OF_DTYPE[layout.float_dtype])
             self._plans[key] = p
         return p
 
@@ -244,6 +244,41 @@ class Engine:
             return a.layout
         lay = BucketLayout.from_state_dict(module.state_dict())
         # share one layout object per signature so plans/staging are reused
+        return self._layouts.setdefault(lay.signature, lay)
+
+    def _native16(self, global_model, client_models) -> Optional[torch.dtype]:
+        """The 16-bit dtype a round can be reduced in natively, or None: the
+        summation order is torch's CPU one, the global and every client sit
+        on one CUDA device, and every non-int64 key of all of them has the one
+        dtype, fp16 or bf16 (model.half() / model.bfloat16()).  Anything else
+        — an fp32 key anywhere (widening it is exact in an fp32 bucket, not in
+        a 16-bit one), a host-resident model, the torch-GPU order — keeps the
+        fp32 buckets with per-call staging."""
+        if self.order != "torch_cpu":
+            return None
+        dts, devs = set(), set()
+        for m in (global_model, *client_models):
+            for d, name in _arena.state_owners(m).values():
+                t = d[name]
+                devs.add(t.device)
+                if t.dtype != torch.int64:
+                    dts.add(t.dtype)
+            if len(dts) > 1 or len(devs) > 1:
+                return None
+        if len(devs) != 1 or next(iter(devs)).type != "cuda":
+            return None
+        return native16_dtype(dts)
+
+    def round_layout(self, global_model: torch.nn.Module,
+                     client_models: Sequence[torch.nn.Module]) -> BucketLayout:
+        """The layout a round over these modules is bound with: the global
+        model's (layout_of), native 16-bit when the round qualifies
+        (_native16) and the fp32 one otherwise."""
+        lay = self.layout_of(global_model)
+        h16 = self._native16(global_model, client_models)
+        if (lay.float_dtype if lay.native16 else None) == h16:
+            return lay
+        lay = BucketLayout.from_state_dict(global_model.state_dict(), native16=h16 is not None)
         return self._layouts.setdefault(lay.signature, lay)
 
     # ------------------------------------------------------------- core --
@@ -325,7 +360,7 @@ class Engine:
         if n == 0:
             raise RuntimeError("stack expects a non-empty TensorList")
         _require_gpu()
-        layout = self.layout_of(global_model)
+        layout = self.round_layout(global_model, client_models)
         with slab.expecting(n + 1):   # a new slab sized for this round's buckets
             ga = get_arena(global_model, layout)
             cas = [get_arena(c, layout) for c in client_models]
@@ -533,7 +568,7 @@ def server_aggregate_split(global_model_a, global_model_b, models_a, models_b):
             # a bound round exists only for pairs without extra keys
             if e.try_bound_round(g, pairs):
                 return
-            layout = e.layout_of(g)
+            layout = e.round_layout(g, pairs)
             arenas = [get_arena(p, layout) for p in pairs]
             if not any(a.extra_keys for a in arenas):
                 e.reduce_modules(g, pairs)

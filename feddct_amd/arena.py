@@ -25,7 +25,7 @@ import torch
 from torch.autograd.graph import increment_version
 
 from . import slab
-from .layout import KIND_I64, KIND_PACKF, BucketLayout
+from .layout import KIND_H16, KIND_I64, KIND_PACKF, BucketLayout
 
 # The per-call checks and version bumps in C (csrc/shim.cpp, built by
 # build.py); the Python loops below define the same semantics and run when
@@ -68,7 +68,8 @@ def state_owners(module: torch.nn.Module) -> Dict[str, Tuple[dict, str]]:
 
 
 def alloc_buckets(layout: BucketLayout, device: torch.device, pinned: bool = False):
-    """A zeroed (fp32, int64) bucket pair.  On a GPU the fp32 bucket is
+    """A zeroed (floating, int64) bucket pair; the floating bucket is fp32,
+    or the layout's 16-bit dtype (BucketLayout native16).  On a GPU it is
     carved from a shared slab (slab.py: one allocation under many buckets
     reads ~8 % faster than as many separate allocations on some boxes); it
     is still a storage of its own, so torch.save of the module writes only
@@ -76,9 +77,9 @@ def alloc_buckets(layout: BucketLayout, device: torch.device, pinned: bool = Fal
     device = torch.device(device)
     if device.type == "cpu":
         kw = dict(pin_memory=True) if pinned and torch.cuda.is_available() else {}
-        return (torch.zeros(max(layout.f32_numel, 64), dtype=torch.float32, **kw),
+        return (torch.zeros(max(layout.f32_numel, 64), dtype=layout.float_dtype, **kw),
                 torch.zeros(max(layout.i64_numel, 1), dtype=torch.int64, **kw))
-    f32 = slab.carve(max(layout.f32_numel, 64), torch.float32, device)
+    f32 = slab.carve(max(layout.f32_numel, 64), layout.float_dtype, device)
     i64 = torch.zeros(max(layout.i64_numel, 1), dtype=torch.int64, device=device)
     return f32, i64
 
@@ -113,6 +114,13 @@ class ModuleArena:
                 raise TypeError(
                     f"state_dict key {s.key!r}: module dtype {t.dtype} cannot be staged in "
                     f"the global model's {s.dtype} slot")
+            if s.kind == KIND_H16 and t.dtype != s.dtype:
+                # a 16-bit bucket holds the keys' own bits: a key of another
+                # dtype has no exact place in it (the engine lays such a
+                # round out in fp32 instead, aggregate.py)
+                raise TypeError(
+                    f"state_dict key {s.key!r}: module dtype {t.dtype} does not match the "
+                    f"native {s.dtype} layout")
             if s.alias_of is not None:
                 a = tensors[s.alias_of]
                 if (t.data_ptr() != a.data_ptr() or t.stride() != a.stride()
@@ -263,7 +271,8 @@ def _part_bases(layout: BucketLayout, f32: torch.Tensor, i64: torch.Tensor, part
             lo = min(s.offset for s in sl)
             hi = max(s.offset + s.numel for s in sl)
             if not is64:
-                hi = min(-(-hi // 64) * 64, bucket.numel())
+                pad = 128 if layout.native16 else 64   # 256 B
+                hi = min(-(-hi // pad) * pad, bucket.numel())
             es = bucket.element_size()
             st = bucket.untyped_storage()[lo * es:hi * es]
             base = torch.empty(0, dtype=bucket.dtype, device=bucket.device).set_(

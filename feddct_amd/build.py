@@ -10,8 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # in parallel (one unit held them all: 5 minutes of device compilation)
 SRCS = [os.path.join(HERE, "csrc", f) for f in
         ("fedagg.hip", "fedagg_k1.hip", "fedagg_k2.hip", "fedagg_k2w.hip", "fedagg_k4.hip",
-         "prox.hip")]
+         "fedagg_h16.hip", "prox.hip")]
 HEADERS = [os.path.join(HERE, "csrc", "common.h"), os.path.join(HERE, "csrc", "reduce_impl.h"),
+           os.path.join(HERE, "csrc", "h16.h"),
            os.path.join(HERE, "..", "include", "fedagg.h")]
 DEPS = SRCS + HEADERS
 OUT = os.path.join(HERE, "libfedagg.so")

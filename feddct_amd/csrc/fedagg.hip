@@ -49,6 +49,7 @@ int fa::set_err(int code, const char* fmt, ...) {
 }
 
 #include "reduce_impl.h"
+#include "h16.h"
 
 // the reduce kernels' launchers are instantiated in the fedagg_k*.hip units
 FA_K_UNITS(extern)
@@ -841,6 +842,10 @@ struct fa_plan {
   unsigned flags = 0;
   bool has32 = false;  // the tile table touches the fp32 bucket
   bool has64 = false;  // ... the int64 bucket
+  // element type of the floating bucket (fa_plan_create_elem).  A 16-bit
+  // plan holds the plain table only (no alt, no balanced tables), info and
+  // tiles in 16-bit elements, vec_u = 16-B loads per lane per client
+  int elem = FA_ELEM_F32;
   int order = FA_ORDER_TORCH_CPU;
   int order_n = 0;        // FA_ORDER_TORCH_GPU: the client count it was cut for
   int tgpu_batch = 16;    // ... rows per load batch of its S = 1 tiles (8 for N < 16)
@@ -929,10 +934,12 @@ void push_scalar(std::vector<Tile>* t, int64_t start, int64_t count, int kind) {
     t->push_back(Tile{start + c, (int32_t)std::min<int64_t>(kBlock, count - c), kind});
 }
 
+// valign: elements per 16-B vector (4 fp32, 8 fp16 / bf16): a cascade body is
+// vectorised when it starts and ends on that boundary.
 int build_tiles(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, int tile_elems,
-                unsigned flags, std::vector<Tile>* out, fa_plan_info* info) {
+                unsigned flags, std::vector<Tile>* out, fa_plan_info* info, int valign = 4) {
   std::vector<Tile> vec, tail;
-  // Maximal runs of cascade-order elements, 4-aligned (vectorisable).
+  // Maximal runs of cascade-order elements, 16-B aligned (vectorisable).
   int64_t run_s = -1, run_e = -1;
   auto flush = [&]() {
     if (run_s < 0) return;
@@ -954,7 +961,7 @@ int build_tiles(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, 
     }
     const int64_t b = body_len(M);
     if (b > 0) {
-      if (g.offset % 4 == 0) {
+      if (g.offset % valign == 0 && b % valign == 0) {
         const bool extend = run_s >= 0 && (run_e == g.offset ||
                                            ((flags & FA_PLAN_GAPS_ARE_PADDING) && run_e <= g.offset));
         if (!extend) flush();
@@ -1440,6 +1447,80 @@ extern "C" {
 const char* fa_version(void) { return FA_VERSION_STR; }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 
+// A 16-bit plan (fa_plan_create_elem, FA_ELEM_F16 / FA_ELEM_BF16): the
+// plain table of the layout cut at 16-B vectors of 8 elements; its kernels
+// (fedagg_h16.hip) take one table at every client count.
+static int check_elem(int elem, int* tile_elems, const char* who) {
+  if (elem != FA_ELEM_F32 && elem != FA_ELEM_F16 && elem != FA_ELEM_BF16)
+    return set_err(FA_E_INVAL, "%s: elem must be FA_ELEM_F32, FA_ELEM_F16 or FA_ELEM_BF16 (got %d)",
+                   who, elem);
+  if (elem == FA_ELEM_F32) return FA_OK;
+  if (*tile_elems == 0) *tile_elems = fa_h16::kDefaultU * fa_h16::kTile;
+  if (*tile_elems != fa_h16::kTile && *tile_elems != 2 * fa_h16::kTile)
+    return set_err(FA_E_INVAL, "%s: a 16-bit plan's tile_elems must be 2048 or 4096 (got %d)", who,
+                   *tile_elems);
+  return FA_OK;
+}
+
+static int plan_create_h16(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
+                           int nseg64, int64_t i64_numel, int tile_elems, unsigned flags, int elem,
+                           fa_plan** out) {
+  std::vector<fa_seg> s32, s64;
+  int rc = check_segs(seg32, nseg32, f32_numel, "16-bit", &s32);
+  if (rc) return rc;
+  rc = check_segs(seg64, nseg64, i64_numel, "int64", &s64);
+  if (rc) return rc;
+  fa_plan* p = new fa_plan();
+  p->elem = elem;
+  p->info.f32_numel = f32_numel;
+  p->info.i64_numel = i64_numel;
+  p->info.tile_elems = tile_elems;
+  p->vec_u = tile_elems / fa_h16::kTile;
+  p->flags = flags | FA_PLAN_TUNE_NO_BALANCE;  // the plain table is the one launched
+  // the broadcast copies the bucket's bytes flat, as numel / 2 floats
+  p->flat_bcast = (flags & FA_PLAN_GAPS_ARE_PADDING) && f32_numel % 2 == 0 &&
+                  covers_with_padding(s32, f32_numel, 128) &&
+                  covers_with_padding(s64, i64_numel, 1);
+  std::vector<Tile> tiles;
+  rc = build_tiles(s32, s64, tile_elems, flags, &tiles, &p->info, fa_h16::kVec);
+  if (rc) {
+    delete p;
+    return rc;
+  }
+  set_kinds(p, tiles);
+  hipError_t e = hipGetDevice(&p->device);
+  if (e == hipSuccess) e = upload_tables(p, tiles, {});
+  if (e != hipSuccess) {
+    (void)fa_plan_destroy(p);
+    return set_err(FA_E_HIP, "fa_plan_create_elem: %s", hipGetErrorString(e));
+  }
+  *out = p;
+  return FA_OK;
+}
+
+int fa_plan_create_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
+                        int nseg64, int64_t i64_numel, int tile_elems, unsigned flags, int elem,
+                        fa_plan** out) {
+  if (elem == FA_ELEM_F32)
+    return fa_plan_create(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
+                          out);
+  if (!out) return set_err(FA_E_INVAL, "fa_plan_create_elem: out is NULL");
+  *out = nullptr;
+  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
+    return set_err(FA_E_INVAL, "fa_plan_create_elem: unknown flag bits 0x%x",
+                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
+  if (f32_numel < 0 || i64_numel < 0) return set_err(FA_E_INVAL, "negative bucket size");
+  const int rc = check_elem(elem, &tile_elems, "fa_plan_create_elem");
+  if (rc) return rc;
+  return plan_create_h16(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
+                         elem, out);
+}
+
+int fa_plan_elem(const fa_plan* plan) {
+  if (!plan) return set_err(FA_E_INVAL, "fa_plan_elem: plan is NULL");
+  return plan->elem;
+}
+
 int fa_plan_create(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
                    int nseg64, int64_t i64_numel, int tile_elems, unsigned flags,
                    fa_plan** out) {
@@ -1899,6 +1980,41 @@ int fa_plan_build_host(const fa_seg* seg32, int nseg32, int64_t f32_numel, const
   return FA_OK;
 }
 
+int fa_plan_build_host_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                            const fa_seg* seg64, int nseg64, int64_t i64_numel, int tile_elems,
+                            unsigned flags, int elem, fa_tile_desc* tiles, int cap,
+                            fa_plan_info* info) {
+  if (elem == FA_ELEM_F32)
+    return fa_plan_build_host(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems,
+                              flags, tiles, cap, info);
+  if (!info) return set_err(FA_E_INVAL, "fa_plan_build_host_elem: info is NULL");
+  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
+    return set_err(FA_E_INVAL, "fa_plan_build_host_elem: unknown flag bits 0x%x",
+                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
+  int rc = check_elem(elem, &tile_elems, "fa_plan_build_host_elem");
+  if (rc) return rc;
+  std::vector<fa_seg> s32, s64;
+  rc = check_segs(seg32, nseg32, f32_numel, "16-bit", &s32);
+  if (rc) return rc;
+  rc = check_segs(seg64, nseg64, i64_numel, "int64", &s64);
+  if (rc) return rc;
+  fa_plan_info in{};
+  in.f32_numel = f32_numel;
+  in.i64_numel = i64_numel;
+  in.tile_elems = tile_elems;
+  std::vector<Tile> t;
+  rc = build_tiles(s32, s64, tile_elems, flags, &t, &in, fa_h16::kVec);
+  if (rc) return rc;
+  *info = in;
+  if (tiles) {
+    if (cap < (int)t.size())
+      return set_err(FA_E_RANGE, "fa_plan_build_host_elem: %d tiles, capacity %d", (int)t.size(),
+                     cap);
+    for (size_t i = 0; i < t.size(); ++i) tiles[i] = fa_tile_desc{t[i].start, t[i].count, t[i].kind};
+  }
+  return FA_OK;
+}
+
 int fa_plan_create_from_tiles(const fa_tile_desc* tiles, int ntiles, int64_t f32_numel,
                               int64_t i64_numel, int tile_elems, unsigned flags,
                               fa_plan** out) {
@@ -1997,7 +2113,8 @@ extern "C++" template <int G>
 void launch_bcast2(const fa_plan* plan, ReduceArgs& a, int ntiles, uint32_t groups,
                    uint32_t gsize, hipStream_t st) {
   if (plan->flat_bcast) {
-    const int64_t f = plan->has32 ? plan->info.f32_numel : 0;
+    // (a 16-bit bucket is copied as numel / 2 floats: the same bytes)
+    const int64_t f = plan->has32 ? plan->info.f32_numel / (plan->elem == FA_ELEM_F32 ? 1 : 2) : 0;
     const int64_t i = plan->has64 ? plan->info.i64_numel : 0;
     const int64_t parts = f > 0 ? std::max<int64_t>(1, (f / 4 + kBlock - 1) / kBlock) : 0;
     const int64_t np = parts + (i > 0 ? 1 : 0);
@@ -2143,6 +2260,11 @@ int fa_plan_launch_shape(const fa_plan* plan, int n, int weighted, int* ntiles, 
     *slots = 0;
     return FA_OK;
   }
+  if (plan->elem != FA_ELEM_F32) {  // one table, launched as it is
+    *ntiles = plan->nt_dev;
+    *slots = 0;
+    return FA_OK;
+  }
   const Launch L = select_launch(plan, n, weighted != 0, 0);
   *ntiles = L.nt;
   *slots = L.slots ? L.slots
@@ -2159,6 +2281,12 @@ int fa_plan_launch_form(const fa_plan* plan, int n, int weighted, int* tile_elem
     *tile_elems = 0;
     *batch = 0;
     *pipe = 0;
+    return FA_OK;
+  }
+  if (plan->elem != FA_ELEM_F32) {  // the client loop, one client per step
+    *tile_elems = plan->info.tile_elems;
+    *batch = 1;
+    *pipe = 1;
     return FA_OK;
   }
   const Launch L = select_launch(plan, n, weighted != 0, 0);
@@ -2187,6 +2315,13 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
     return set_err(FA_E_INVAL, "fa_reduce: bad flags");
   if (plan->order == FA_ORDER_TORCH_GPU && weights)
     return set_err(FA_E_INVAL, "fa_reduce: the torch-GPU order is the reference's unweighted mean");
+  const bool h16 = plan->elem != FA_ELEM_F32;
+  if (h16 && (flags & FA_F_SUM_ONLY))
+    return set_err(FA_E_INVAL, "fa_reduce: FA_F_SUM_ONLY is not defined for a 16-bit plan (the "
+                               "ordered fp32 sum has no 16-bit slot to go to)");
+  if (h16 && (flags & (FA_F_BCAST | FA_F_BCAST_ONLY)) && !plan->flat_bcast)
+    return set_err(FA_E_INVAL, "fa_reduce: a 16-bit plan broadcasts the bucket's bytes flat and "
+                               "needs FA_PLAN_GAPS_ARE_PADDING with full coverage");
   const fa_plan_info& in = plan->info;
   if (plan->info.ntiles == 0) return FA_OK;
   ReduceArgs a;
@@ -2310,6 +2445,23 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
     if (e != hipSuccess) return set_err(FA_E_HIP, "torch-GPU-order launch: %s", hipGetErrorString(e));
     return FA_OK;
   }
+  if (h16) {
+    // the 16-bit kernels (fedagg_h16.hip) over the plan's one table, then the
+    // broadcast's flat copy of the result bucket
+    a.nscalar = plan->ns_dev;
+    a.sidx = plan->d_sidx;
+    a.ntiles = plan->nt_dev;
+    const bool bc = (flags & FA_F_BCAST) != 0;
+    a.flags &= ~FA_F_BCAST;
+    hipError_t e = fa_h16::launch(a, plan->nt_dev, plan->elem, plan->vec_u, weights != nullptr, st);
+    if (e == hipSuccess && bc) e = launch_bcast(plan, a, n, plan->nt_dev, st);
+    if (table) {
+      hipError_t e2 = hipFreeAsync(table, st);
+      if (e == hipSuccess) e = e2;
+    }
+    if (e != hipSuccess) return set_err(FA_E_HIP, "16-bit reduce launch: %s", hipGetErrorString(e));
+    return FA_OK;
+  }
   const Launch L = select_launch(plan, n, weights != nullptr, flags);
   a.tiles = L.tiles;
   a.nscalar = L.ns;
@@ -2354,6 +2506,9 @@ int fa_reduce_chain(const fa_plan* plan, const float* const* c32, int n, const f
   if (n < 1 || ch->row0 < 0 || ch->row0 + n > nt)
     return set_err(FA_E_INVAL, "fa_reduce_chain: rows [%d,+%d) outside the %d-row reduction",
                    ch->row0, n, nt);
+  if (plan->elem != FA_ELEM_F32)
+    return set_err(FA_E_INVAL, "fa_reduce_chain: not defined for a 16-bit plan (the state planes "
+                               "are fp32; chain fp32 buckets)");
   if (plan->has64 || plan->info.ntiles_tail > 0)
     return set_err(FA_E_INVAL,
                    "fa_reduce_chain: the plan holds scalar tiles (tails, M==1, int64); chain "

@@ -1,0 +1,322 @@
+// fedagg_h16.hip — the reduce over fp16 / bf16 buckets (model.half() /
+// model.bfloat16() clients; fa_plan_create_elem).  The reference's line,
+//
+//     torch.stack([m.state_dict()[k].float() for m in clients], 0).mean(0)
+//
+// followed by load_state_dict's copy_ into the 16-bit key: every value is
+// widened exactly to fp32, summed in fp32 in torch's CPU order (the orders of
+// reduce_impl.h, unchanged), divided by N, and the fp32 mean rounded to
+// nearest-even into the key's type.  The kernels read the clients' 16-bit
+// buckets directly — half the bytes of the fp32 staging this replaces — and
+// write a 16-bit result.
+//
+// Vector tiles: each lane owns 8 adjacent columns per 16-B load (U loads per
+// client: tiles of U * 2048 elements) and walks the clients serially with
+// the next client's loads issued before the current client's adds
+// (reduce_impl.h pipe2_clients' rhythm: one client in flight per wave).  All
+// four cascade levels are carried at every N: levels 2-3 stay +0 below 256
+// clients and x + (+0) == x for every value a +0-seeded sum can hold.
+// Scalar columns (ILP-4 tails, M == 1 keys, unaligned or 4-column cascade
+// bodies, int64 keys) run reduce_impl.h's cascade_seq / ilp4_seq / inner_seq
+// from an LDS stage filled through a 16-bit source.
+//
+// Its own translation unit and its own kernel family: reduce_impl.h's fp32
+// kernels are not templated on the element type (code a launch never runs
+// cost other instances 0.7-2.5 %).
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "common.h"
+#include "h16.h"
+
+namespace fa_h16 {
+using namespace fa_k;
+
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) const u4 gcu4;
+
+// ------------------------------------------------------------ conversions --
+// Exact widening.  bf16 is the upper half of an fp32.  fp16: v_cvt_f32_f16
+// (subnormals kept: the kernels run with the default denormal mode); the
+// empty asm pins the converted value in a register, so the compiler cannot
+// fold the conversion into a mixed-precision multiply-add.
+template <int EL>
+__device__ __forceinline__ float widen(uint32_t h) {  // h: the 16 bits, zero-extended
+  if constexpr (EL == FA_ELEM_BF16) {
+    return __uint_as_float(h << 16);
+  } else {
+    float f = (float)__builtin_bit_cast(_Float16, (uint16_t)h);
+    asm volatile("" : "+v"(f));
+    return f;
+  }
+}
+// The two elements of one dword, low address first.
+template <int EL>
+__device__ __forceinline__ void widen2(uint32_t w, float* lo, float* hi) {
+  if constexpr (EL == FA_ELEM_BF16) {
+    *lo = __uint_as_float(w << 16);
+    *hi = __uint_as_float(w & 0xffff0000u);
+  } else {
+    *lo = widen<EL>(w & 0xffffu);
+    *hi = widen<EL>(w >> 16);
+  }
+}
+
+// fp32 -> 16 bits, round to nearest-even, as torch's CPU copy_ (c10's
+// round_to_nearest_even for bf16, the IEEE conversion for fp16: overflow to
+// +-inf, subnormal results kept).  A NaN gives a quiet NaN.
+template <int EL>
+__device__ __forceinline__ uint32_t narrow(float x) {
+  if constexpr (EL == FA_ELEM_BF16) {
+    const uint32_t u = __float_as_uint(x);
+    if (x != x) return 0x7fc0u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+  } else {
+    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x);
+  }
+}
+template <int EL>
+__device__ __forceinline__ uint32_t narrow2(float lo, float hi) {
+  return narrow<EL>(lo) | (narrow<EL>(hi) << 16);
+}
+
+template <int EL>
+__device__ __forceinline__ void widen8(u4 v, f4* a, f4* b) {
+  float f[8];
+  widen2<EL>(v.x, &f[0], &f[1]);
+  widen2<EL>(v.y, &f[2], &f[3]);
+  widen2<EL>(v.z, &f[4], &f[5]);
+  widen2<EL>(v.w, &f[6], &f[7]);
+  *a = f4{f[0], f[1], f[2], f[3]};
+  *b = f4{f[4], f[5], f[6], f[7]};
+}
+
+// 16-B non-temporal load of vector `vidx` (8 elements) past a uniform base.
+__device__ __forceinline__ u4 ldu4(const uint16_t* base, uint32_t vidx) {
+  return __builtin_nontemporal_load((gcu4*)base + vidx);
+}
+// The result store: a buffer store with the sc1 policy bit, the fp32
+// reduce's (reduce_impl.h st_out: the broadcast reads the result next).
+__device__ __forceinline__ void st_sc1(uint16_t* base, uint32_t vidx, u4 v) {
+  const __amdgpu_buffer_rsrc_t r =
+      __builtin_amdgcn_make_buffer_rsrc(base, (short)0, 0x7fffffff, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)(16 * vidx), 0, 16);
+}
+
+// --------------------------------------------------------- vector tiles ----
+// Client i's bucket and weight through scalar loads only: the kernarg arrays
+// (n <= kInline) or the device table through the constant address space.
+template <bool TAB>
+__device__ __forceinline__ const uint16_t* cptr16(KArgs& a, int i) {
+  if constexpr (TAB) return (const uint16_t*)((const FA_CONST f32p*)a.tab32)[i];
+  else return (const uint16_t*)a.c32[i];
+}
+template <bool TAB>
+__device__ __forceinline__ float cw16(KArgs& a, int i) {
+  if constexpr (TAB) return ((const FA_CONST float*)a.tabw)[i];
+  else return a.w[i];
+}
+
+// The clients in slot order, the next client's loads issued before the
+// current client's adds.  Lane vector u holds columns 8 * vi[u] .. + 7 in
+// accumulators 2u (first four) and 2u + 1.
+template <int EL, int U, bool FULL, bool W, bool TAB>
+__device__ __forceinline__ void clients16(KArgs& a, Acc<2 * U, true>& A, int n, int64_t start,
+                                          const uint32_t (&vi)[U], const bool (&ok)[U], int lp,
+                                          int mask) {
+  const u4 zero = u4{0u, 0u, 0u, 0u};
+  u4 cur[U], nxt[U];
+  {
+    const uint16_t* p = cptr16<TAB>(a, 0) + start;
+#pragma unroll
+    for (int u = 0; u < U; ++u) cur[u] = (FULL || ok[u]) ? ldu4(p, vi[u]) : zero;
+  }
+  for (int b = 0; b < n; ++b) {
+    if (b + 1 < n) {
+      const uint16_t* p = cptr16<TAB>(a, b + 1) + start;
+#pragma unroll
+      for (int u = 0; u < U; ++u) nxt[u] = (FULL || ok[u]) ? ldu4(p, vi[u]) : zero;
+    }
+    float wb = 0.f;
+    if constexpr (W) wb = cw16<TAB>(a, b);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      f4 x0, x1;
+      widen8<EL>(cur[u], &x0, &x1);
+      if constexpr (W) {
+        x0 = mul4s(x0, wb);
+        x1 = mul4s(x1, wb);
+      }
+      A.l0[2 * u] = add4(A.l0[2 * u], x0);
+      A.l0[2 * u + 1] = add4(A.l0[2 * u + 1], x1);
+    }
+    promote<2 * U, true>(A, b + 1, lp, mask);
+#pragma unroll
+    for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+  }
+}
+
+template <int EL, int U, bool FULL, bool W>
+__device__ __forceinline__ void tile_vec16(KArgs& a, int64_t start, int count) {
+  const int n = a.n;
+  const int lp = level_power(n);
+  const int mask = (1 << lp) - 1;
+  Acc<2 * U, true> A;
+  uint32_t vi[U];
+  bool ok[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    // block-strided: lane t takes vectors t, t + 256
+    const int v = (int)threadIdx.x + u * kBlock;
+    vi[u] = (uint32_t)v;
+    ok[u] = FULL || kVec * v < count;
+  }
+#pragma unroll
+  for (int j = 0; j < 2 * U; ++j)
+    A.l0[j] = A.l1[j] = A.l2[j] = A.l3[j] = f4{0.f, 0.f, 0.f, 0.f};
+  if (n <= kInline) clients16<EL, U, FULL, W, false>(a, A, n, start, vi, ok, lp, mask);
+  else clients16<EL, U, FULL, W, true>(a, A, n, start, vi, ok, lp, mask);
+  const float fn = (float)n;
+  uint16_t* out = (uint16_t*)a.out32 + start;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (!ok[u]) continue;
+    f4 r[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f4 s = add4(A.l0[2 * u + h], A.l1[2 * u + h]);
+      s = add4(s, A.l2[2 * u + h]);
+      s = add4(s, A.l3[2 * u + h]);
+      r[h] = W ? s : div4s(s, fn);
+    }
+    st_sc1(out, vi[u],
+           u4{narrow2<EL>(r[0].x, r[0].y), narrow2<EL>(r[0].z, r[0].w),
+              narrow2<EL>(r[1].x, r[1].y), narrow2<EL>(r[1].z, r[1].w)});
+  }
+}
+
+// -------------------------------------------------------- scalar columns ---
+// The value each order reads from a 16-bit bucket: widened, and in a
+// weighted call multiplied by the client's weight (rounded before any add).
+template <int EL>
+struct SrcH16 {
+  KArgs& a;
+  bool weighted;
+  __device__ float operator()(int i, int64_t e) const {
+    const float x = widen<EL>(((const uint16_t*)cptr32(a, i))[e]);
+    return weighted ? __fmul_rn(x, cw(a, i)) : x;
+  }
+};
+
+// reduce_impl.h scalar_column with a 16-bit result for the floating kinds.
+template <int EL, bool W, class SrcF, class SrcI>
+__device__ __forceinline__ void scalar_column16(KArgs& a, const SrcF& sf, const SrcI& si,
+                                                int64_t e, int kind) {
+  const int n = a.n;
+  const float fn = (float)n;
+  if (kind <= K_F32_INNER) {
+    float s;
+    if (kind == K_F32_CASC_S) s = cascade_seq(sf, e, 0, 1, n);
+    else if (kind == K_F32_ILP4) s = ilp4_seq(sf, e, 0, 1, n);
+    else s = inner_seq(sf, e, n);
+    s = __fadd_rn(0.f, s);  // sum_out: out (=+0) += value
+    ((uint16_t*)a.out32)[e] = (uint16_t)narrow<EL>(W ? s : __fdiv_rn(s, fn));
+  } else {
+    float s;
+    if (kind == K_I64_CASC) s = cascade_seq(si, e, 0, 1, n);
+    else if (kind == K_I64_ILP4) s = ilp4_seq(si, e, 0, 1, n);
+    else s = inner_seq(si, e, n);
+    s = __fadd_rn(0.f, s);
+    a.out64[e] = (int64_t)__fdiv_rn(s, fn);  // copy_: fp32 -> int64 truncates
+  }
+}
+
+// reduce_impl.h tile_scalar_packed over a 16-bit floating bucket: packed tile
+// k's up to kPackCols columns (entries at sidx[k * kPackCols ..], -1 unused),
+// their N rows staged into LDS with independent loads, each column's order
+// run from LDS by one lane of wave 0.
+template <int EL, bool W>
+__device__ __forceinline__ void tile_scalar16(KArgs& a, int k) {
+  __shared__ float stage[kStageFloats];
+  const int n = a.n;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t* ents = a.sidx + (int64_t)k * kPackCols;
+  if (n > kStageFloats) {  // direct loads, one column per lane of wave 0
+    if (wv == 0) {
+      const int64_t ent = ents[lane];
+      if (ent >= 0)
+        scalar_column16<EL, W>(a, SrcH16<EL>{a, W}, SrcI64{a}, ent >> 4, (int)(ent & 15));
+    }
+    return;
+  }
+  const int sub = min(kPackCols, kStageFloats / n);  // columns staged at once
+  for (int c0 = 0; c0 < kPackCols; c0 += sub) {
+    const int m = min(sub, kPackCols - c0);
+    const int64_t ent = lane < m ? ents[c0 + lane] : -1;
+    const bool mine = ent >= 0;
+    const int64_t e = mine ? ent >> 4 : 0;
+    const int kind = mine ? (int)(ent & 15) : K_F32_ILP4;
+    const bool flt = kind <= K_F32_INNER;
+    constexpr int R = 8;  // rows in flight per lane
+    for (int i0 = wv; i0 < n; i0 += 4 * R) {
+      float x[R];
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        const int r = i0 + 4 * u;
+        if (r < n && mine) x[u] = flt ? SrcH16<EL>{a, W}(r, e) : SrcI64{a}(r, e);
+      }
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        const int r = i0 + 4 * u;
+        if (r < n && mine) stage[r * m + lane] = x[u];
+      }
+    }
+    __syncthreads();
+    if (wv == 0 && mine) {
+      const SrcLdsCol src{stage, m, lane};
+      scalar_column16<EL, W>(a, src, src, e, kind);
+    }
+    __syncthreads();
+  }
+}
+
+// ----------------------------------------------------------------- kernel --
+// One workgroup per tile; the packed scalar tiles lead the table.
+template <int EL, int U, bool W>
+__global__ __launch_bounds__(kBlock) void h16_round_kernel(ReduceArgs args) {
+  (void)args;
+  KArgs& a = *(KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  const int ti = blockIdx.x;
+  if (ti < a.nscalar) {
+    tile_scalar16<EL, W>(a, ti);
+    return;
+  }
+  const Tile t = a.tiles[ti];
+  if (t.kind != K_F32_VEC) return;
+  if (t.count == U * kTile) tile_vec16<EL, U, true, W>(a, t.start, t.count);
+  else tile_vec16<EL, U, false, W>(a, t.start, t.count);
+}
+
+template <int EL, int U>
+static hipError_t launch_w(const ReduceArgs& a, int ntiles, bool w, hipStream_t st) {
+  if (w) hipLaunchKernelGGL((h16_round_kernel<EL, U, true>), dim3(ntiles), dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL((h16_round_kernel<EL, U, false>), dim3(ntiles), dim3(kBlock), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch(const ReduceArgs& a, int ntiles, int elem, int u, bool weighted,
+                  hipStream_t st) {
+  if (ntiles <= 0) return hipSuccess;
+  if (elem == FA_ELEM_F16)
+    return u == 1 ? launch_w<FA_ELEM_F16, 1>(a, ntiles, weighted, st)
+                  : launch_w<FA_ELEM_F16, 2>(a, ntiles, weighted, st);
+  if (elem == FA_ELEM_BF16)
+    return u == 1 ? launch_w<FA_ELEM_BF16, 1>(a, ntiles, weighted, st)
+                  : launch_w<FA_ELEM_BF16, 2>(a, ntiles, weighted, st);
+  return hipErrorInvalidValue;
+}
+
+}  // namespace fa_h16

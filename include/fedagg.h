@@ -131,6 +131,37 @@ int fa_plan_create(const fa_seg *seg32, int nseg32, int64_t f32_numel,
                    int tile_elems, unsigned flags, fa_plan **out);
 int fa_plan_destroy(fa_plan *plan);
 
+/* ---- element type of the floating bucket (a property of the plan) ---------
+ * FA_ELEM_F32 (fa_plan_create): fp32 buckets, everything above.
+ * FA_ELEM_F16 / FA_ELEM_BF16: the floating bucket holds IEEE half / bfloat16
+ *   elements, as model.half() / model.bfloat16() clients hold them.  Per key
+ *   the result is the reference's: every value widened exactly to fp32, the
+ *   fp32 sum in the same torch order, /N (or the weighted sum of
+ *   fp32(float(x_i) * w_i), no division), then rounded to nearest-even into
+ *   the 16-bit type as torch's CPU copy_ rounds it (a NaN result is a NaN).
+ *   Offsets, counts, f32_numel and fa_plan_info.tile_elems are in 16-bit
+ *   ELEMENTS; vector tiles start and end on 16-B boundaries (start % 8 == 0,
+ *   count % 8 == 0), so a key whose offset is not a multiple of 8, and the
+ *   4-column cascade body of a key of 4..7 elements, take the scalar cascade.
+ *   tile_elems: 2048 or 4096 (0 = default).  fa_reduce / fa_reduce_tab
+ *   dispatch on the plan: c32[i] and out32 are then the 16-bit buckets (still
+ *   16-B aligned); the int64 bucket is unchanged.  FA_F_BCAST /
+ *   FA_F_BCAST_ONLY copy the bucket's bytes flat and need a plan whose
+ *   segments cover it (FA_PLAN_GAPS_ARE_PADDING, no gap of >= 128 elements)
+ *   and an even f32_numel.  Refused with FA_E_INVAL on a 16-bit plan:
+ *   FA_F_SUM_ONLY and fa_reduce_chain; fa_plan_create_order and
+ *   fa_plan_create_from_tiles make fp32 plans only, as do the multi-GPU
+ *   rounds of libfedagg_comm.so. */
+#define FA_ELEM_F32 0
+#define FA_ELEM_F16 1
+#define FA_ELEM_BF16 2
+int fa_plan_create_elem(const fa_seg *seg32, int nseg32, int64_t f32_numel,
+                        const fa_seg *seg64, int nseg64, int64_t i64_numel,
+                        int tile_elems, unsigned flags, int elem,
+                        fa_plan **out);
+/* The plan's element type (FA_ELEM_*), < 0 on error. */
+int fa_plan_elem(const fa_plan *plan);
+
 /* Host-only tile table of a layout (no device, no allocation): for tests and
  * inspection.  kind: 0 fp32 cascade (16-B vectors), 1 fp32 cascade (scalar),
  * 2 fp32 ILP-4 tail, 3 fp32 M==1, 4/5/6 int64 cascade/ILP-4/M==1.  With
@@ -144,6 +175,13 @@ int fa_plan_build_host(const fa_seg *seg32, int nseg32, int64_t f32_numel,
                        const fa_seg *seg64, int nseg64, int64_t i64_numel,
                        int tile_elems, unsigned flags, fa_tile_desc *tiles,
                        int cap, fa_plan_info *info);
+/* ... of a layout whose floating bucket holds `elem` elements (FA_ELEM_*;
+ * FA_ELEM_F32: fa_plan_build_host's table). */
+int fa_plan_build_host_elem(const fa_seg *seg32, int nseg32, int64_t f32_numel,
+                            const fa_seg *seg64, int nseg64,
+                            int64_t i64_numel, int tile_elems, unsigned flags,
+                            int elem, fa_tile_desc *tiles, int cap,
+                            fa_plan_info *info);
 int fa_plan_get_info(const fa_plan *plan, fa_plan_info *info);
 
 /* A plan over an explicit subset of a layout's tiles (as returned by
