@@ -62,6 +62,7 @@ EXPORTS = [
     "fa_plan_create_order", "fa_table_bytes", "fa_reduce_tab",
     "fa_plan_balance_host", "fa_plan_launch_shape", "fa_plan_launch_form",
     "fa_plan_create_elem", "fa_plan_build_host_elem", "fa_plan_elem",
+    "fa_plan_create_elem_out", "fa_plan_out_elem",
 ]
 
 
@@ -108,6 +109,9 @@ def _load():
         "fa_plan_create_elem": (_I, [_P, _I, _I64, _P, _I, _I64, _I, ctypes.c_uint, _I,
                                      ctypes.POINTER(_P)]),
         "fa_plan_elem": (_I, [_P]),
+        "fa_plan_create_elem_out": (_I, [_P, _I, _I64, _P, _I, _I64, _I, ctypes.c_uint, _I, _I,
+                                         ctypes.POINTER(_P)]),
+        "fa_plan_out_elem": (_I, [_P]),
         "fa_plan_build_host_elem": (_I, [_P, _I, _I64, _P, _I, _I64, _I, ctypes.c_uint, _I, _P, _I,
                                          ctypes.POINTER(FaPlanInfo)]),
         "fa_plan_destroy": (_I, [_P]),
@@ -235,10 +239,23 @@ class Plan:
 
     def __init__(self, segs32, f32_numel, segs64=(), i64_numel=0, tile_elems=0,
                  flags=FA_PLAN_GAPS_ARE_PADDING, tiles=None, order=FA_ORDER_TORCH_CPU, n=0,
-                 elem=FA_ELEM_F32):
+                 elem=FA_ELEM_F32, out_elem=None):
         h = ctypes.c_void_p()
         self.elem = int(elem)
-        if elem != FA_ELEM_F32:
+        # the result bucket's element type (fa_plan_create_elem_out): FA_ELEM_F32
+        # over 16-bit clients is the mixed plan of an fp32 master global
+        self.out_elem = self.elem if out_elem is None else int(out_elem)
+        if out_elem is not None:
+            if order != FA_ORDER_TORCH_CPU or tiles is not None:
+                raise FedaggError("a plan with an output element type is cut from a layout's "
+                                  "segments in torch's CPU order (no tile subsets, no torch-GPU "
+                                  "order)")
+            a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
+            a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
+            check(lib.fa_plan_create_elem_out(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
+                                              int(tile_elems), flags, int(elem), int(out_elem),
+                                              ctypes.byref(h)), "fa_plan_create_elem_out")
+        elif elem != FA_ELEM_F32:
             # a 16-bit floating bucket: the CPU order from a segment list only
             if order != FA_ORDER_TORCH_CPU or tiles is not None:
                 raise FedaggError("a 16-bit plan is cut from a layout's segments in torch's "

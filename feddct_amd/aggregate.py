@@ -207,11 +207,13 @@ class Engine:
     GPU_PLAN_CACHE = 8
 
     def plan(self, layout: BucketLayout, device: torch.device, n: int = 0,
-             order: str = "torch_cpu") -> Optional[_lib.Plan]:
+             order: str = "torch_cpu", master: bool = False) -> Optional[_lib.Plan]:
         """The layout's plan on ``device``.  For the torch-GPU order, the
         plan cut for ``n`` clients, or None when torch itself would split
         some key across blocks there (outside the restated configurations,
-        fa_torch_gpu_config)."""
+        fa_torch_gpu_config).  ``master``: the mixed plan of a native 16-bit
+        client layout under an fp32 master global (fp32 result bucket,
+        fa_plan_create_elem_out)."""
         if order == "torch_gpu":
             key = (layout.signature, device.index, n)
             if key in self._gpu_plans:
@@ -229,12 +231,17 @@ class Engine:
             while len(self._gpu_plans) > self.GPU_PLAN_CACHE:
                 self._gpu_plans.popitem(last=False)
             return p
-        key = (layout.signature, device.index)
+        key = (layout.signature, device.index) + (("<master>",) if master else ())
         p = self._plans.get(key)
         if p is None:
             with torch.cuda.device(device):
-                p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
-                              layout.i64_numel, elem=_lib.ELEM_OF_DTYPE[layout.float_dtype])
+                if master:
+                    p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
+                                  layout.i64_numel, elem=_lib.ELEM_OF_DTYPE[layout.float_dtype],
+                                  out_elem=_lib.FA_ELEM_F32)
+                else:
+                    p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
+                                  layout.i64_numel, elem=_lib.ELEM_OF_DTYPE[layout.float_dtype])
             self._plans[key] = p
         return p
 
@@ -246,40 +253,83 @@ class Engine:
         # share one layout object per signature so plans/staging are reused
         return self._layouts.setdefault(lay.signature, lay)
 
-    def _native16(self, global_model, client_models) -> Optional[torch.dtype]:
-        """The 16-bit dtype a round can be reduced in natively, or None: the
-        summation order is torch's CPU one, the global and every client sit
-        on one CUDA device, and every non-int64 key of all of them has the one
-        dtype, fp16 or bf16 (model.half() / model.bfloat16()).  Anything else
-        — an fp32 key anywhere (widening it is exact in an fp32 bucket, not in
-        a 16-bit one), a host-resident model, the torch-GPU order — keeps the
-        fp32 buckets with per-call staging."""
+    def _round_dtypes(self, global_model, client_models):
+        """(kind, dtype) of a round the 16-bit kernels can reduce natively, or
+        (None, None).  The summation order is torch's CPU one, the global and
+        every client sit on one CUDA device, every non-int64 key of every
+        client has the one dtype, fp16 or bf16 (model.half() /
+        model.bfloat16()), and the global's non-int64 keys are all of that
+        dtype too (kind "native": 16-bit buckets throughout) or all fp32 (kind
+        "mixed": an fp32 master global, which takes the unrounded fp32 mean).
+        Anything else — an fp32 key in a client or a 16-bit one in an
+        otherwise fp32 global (widening is exact in an fp32 bucket, not in a
+        16-bit one), clients of two dtypes, a host-resident model, the
+        torch-GPU order, a 16-bit global over fp32 clients — keeps the fp32
+        buckets with per-call staging."""
         if self.order != "torch_cpu":
-            return None
-        dts, devs = set(), set()
-        for m in (global_model, *client_models):
+            return None, None
+        gdts, cdts, devs = set(), set(), set()
+        for i, m in enumerate((global_model, *client_models)):
+            dts = cdts if i else gdts
             for d, name in _arena.state_owners(m).values():
                 t = d[name]
                 devs.add(t.device)
                 if t.dtype != torch.int64:
                     dts.add(t.dtype)
             if len(dts) > 1 or len(devs) > 1:
-                return None
+                return None, None
         if len(devs) != 1 or next(iter(devs)).type != "cuda":
-            return None
-        return native16_dtype(dts)
+            return None, None
+        h16 = native16_dtype(cdts)
+        if h16 is None:
+            return None, None
+        if gdts <= cdts:   # (a global with no floating key at all included)
+            return "native", h16
+        if gdts == {torch.float32}:
+            return "mixed", h16
+        return None, None
+
+    def _native16(self, global_model, client_models) -> Optional[torch.dtype]:
+        """The 16-bit dtype of an all-16-bit round (_round_dtypes "native"),
+        or None."""
+        kind, h16 = self._round_dtypes(global_model, client_models)
+        return h16 if kind == "native" else None
+
+    def _mixed16(self, global_model, client_models) -> Optional[torch.dtype]:
+        """The clients' 16-bit dtype of a round under an fp32 master global
+        (_round_dtypes "mixed"), or None."""
+        kind, h16 = self._round_dtypes(global_model, client_models)
+        return h16 if kind == "mixed" else None
+
+    def round_layouts(self, global_model: torch.nn.Module,
+                      client_models: Sequence[torch.nn.Module]):
+        """(global's layout, clients' layout) a round over these modules is
+        bound with.  One layout of the global model's keys for both — native
+        16-bit when the round qualifies, the fp32 one otherwise — except in a
+        mixed round: the global takes the master layout (its own fp32 keys at
+        the 16-bit layout's element offsets) and the clients the native
+        16-bit layout of the same keys in their dtype."""
+        lay = self.layout_of(global_model)
+        kind, h16 = self._round_dtypes(global_model, client_models)
+        if kind == "mixed":
+            if not lay.master16:
+                lay = BucketLayout.from_state_dict(global_model.state_dict(), master16=True)
+                lay = self._layouts.setdefault(lay.signature, lay)
+            cl = BucketLayout([(s.key, s.shape, s.dtype if s.dtype == torch.int64 else h16)
+                               for s in lay.slots],
+                              {s.key: s.alias_of for s in lay.slots if s.alias_of is not None},
+                              native16=True)
+            return lay, self._layouts.setdefault(cl.signature, cl)
+        if not lay.master16 and (lay.float_dtype if lay.native16 else None) == h16:
+            return lay, lay
+        lay = BucketLayout.from_state_dict(global_model.state_dict(), native16=h16 is not None)
+        lay = self._layouts.setdefault(lay.signature, lay)
+        return lay, lay
 
     def round_layout(self, global_model: torch.nn.Module,
                      client_models: Sequence[torch.nn.Module]) -> BucketLayout:
-        """The layout a round over these modules is bound with: the global
-        model's (layout_of), native 16-bit when the round qualifies
-        (_native16) and the fp32 one otherwise."""
-        lay = self.layout_of(global_model)
-        h16 = self._native16(global_model, client_models)
-        if (lay.float_dtype if lay.native16 else None) == h16:
-            return lay
-        lay = BucketLayout.from_state_dict(global_model.state_dict(), native16=h16 is not None)
-        return self._layouts.setdefault(lay.signature, lay)
+        """The layout the round's global model is bound with (round_layouts)."""
+        return self.round_layouts(global_model, client_models)[0]
 
     # ------------------------------------------------------------- core --
     def try_bound_round(self, global_model: torch.nn.Module,
@@ -360,9 +410,9 @@ class Engine:
         if n == 0:
             raise RuntimeError("stack expects a non-empty TensorList")
         _require_gpu()
-        layout = self.round_layout(global_model, client_models)
+        glayout, layout = self.round_layouts(global_model, client_models)
         with slab.expecting(n + 1):   # a new slab sized for this round's buckets
-            ga = get_arena(global_model, layout)
+            ga = get_arena(global_model, glayout)
             cas = [get_arena(c, layout) for c in client_models]
         # torch.stack (train_fedavg.py:145) needs the clients on one device;
         # the global may live elsewhere (load_state_dict at :147 copies across)
@@ -382,7 +432,8 @@ class Engine:
         if dev.type == "cuda":
             if ga.device == dev:
                 self._fallback_round = False
-                plan = self._reduce_device(layout, ga.f32, ga.i64, cas, weights, fuse_bcast)
+                plan = self._reduce_device(layout, ga.f32, ga.i64, cas, weights, fuse_bcast,
+                                           master=glayout is not layout)
                 # (a round the torch-GPU order could not restate is never bound:
                 # each such call takes this path, is counted and can be refused)
                 if fuse_bcast and _arena._fa_shim is not None and not self._fallback_round:
@@ -456,13 +507,15 @@ class Engine:
         return st
 
     def _reduce_device(self, layout, out32: torch.Tensor, out64: torch.Tensor,
-                       cas: List[ModuleArena], weights, fuse):
+                       cas: List[ModuleArena], weights, fuse, master=False):
         n = len(cas)
         dev = cas[0].device
         order = self.order
         if order == "torch_gpu" and (weights is not None or n < 2):
             order = "torch_cpu"   # (the GPU order is torch's unweighted mean, N >= 2)
-        plan = self.plan(layout, dev, n, order)
+        # master: a mixed round (torch's CPU order by definition): `layout` is
+        # the clients' 16-bit one, out32 the global's fp32 bucket
+        plan = self.plan(layout, dev, n, order, master)
         if plan is None:   # torch would split a key across blocks at this N
             msg = (f"feddct_amd: torch-GPU summation order is not restated for N={n} on "
                    f"this layout (torch splits a key across blocks)")
@@ -568,7 +621,7 @@ def server_aggregate_split(global_model_a, global_model_b, models_a, models_b):
             # a bound round exists only for pairs without extra keys
             if e.try_bound_round(g, pairs):
                 return
-            layout = e.round_layout(g, pairs)
+            layout = e.round_layouts(g, pairs)[1]
             arenas = [get_arena(p, layout) for p in pairs]
             if not any(a.extra_keys for a in arenas):
                 e.reduce_modules(g, pairs)

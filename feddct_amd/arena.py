@@ -271,7 +271,7 @@ def _part_bases(layout: BucketLayout, f32: torch.Tensor, i64: torch.Tensor, part
             lo = min(s.offset for s in sl)
             hi = max(s.offset + s.numel for s in sl)
             if not is64:
-                pad = 128 if layout.native16 else 64   # 256 B
+                pad = 128 if layout.native16 or layout.master16 else 64   # keys' boundary
                 hi = min(-(-hi // pad) * pad, bucket.numel())
             es = bucket.element_size()
             st = bucket.untyped_storage()[lo * es:hi * es]

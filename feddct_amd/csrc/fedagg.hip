@@ -846,6 +846,10 @@ struct fa_plan {
   // plan holds the plain table only (no alt, no balanced tables), info and
   // tiles in 16-bit elements, vec_u = 16-B loads per lane per client
   int elem = FA_ELEM_F32;
+  // element type of the result bucket (fa_plan_create_elem_out).  == elem but
+  // on a mixed plan: 16-bit clients, FA_ELEM_F32 result (the fp32 master
+  // global), the wide-store reduce and the narrowing broadcast
+  int out_elem = FA_ELEM_F32;
   int order = FA_ORDER_TORCH_CPU;
   int order_n = 0;        // FA_ORDER_TORCH_GPU: the client count it was cut for
   int tgpu_batch = 16;    // ... rows per load batch of its S = 1 tiles (8 for N < 16)
@@ -1464,7 +1468,7 @@ static int check_elem(int elem, int* tile_elems, const char* who) {
 
 static int plan_create_h16(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
                            int nseg64, int64_t i64_numel, int tile_elems, unsigned flags, int elem,
-                           fa_plan** out) {
+                           int out_elem, fa_plan** out) {
   std::vector<fa_seg> s32, s64;
   int rc = check_segs(seg32, nseg32, f32_numel, "16-bit", &s32);
   if (rc) return rc;
@@ -1472,13 +1476,16 @@ static int plan_create_h16(const fa_seg* seg32, int nseg32, int64_t f32_numel, c
   if (rc) return rc;
   fa_plan* p = new fa_plan();
   p->elem = elem;
+  p->out_elem = out_elem;
   p->info.f32_numel = f32_numel;
   p->info.i64_numel = i64_numel;
   p->info.tile_elems = tile_elems;
   p->vec_u = tile_elems / fa_h16::kTile;
   p->flags = flags | FA_PLAN_TUNE_NO_BALANCE;  // the plain table is the one launched
-  // the broadcast copies the bucket's bytes flat, as numel / 2 floats
-  p->flat_bcast = (flags & FA_PLAN_GAPS_ARE_PADDING) && f32_numel % 2 == 0 &&
+  // the broadcast copies the bucket's bytes flat, as numel / 2 floats (a
+  // mixed plan's narrows element by element: any f32_numel)
+  p->flat_bcast = (flags & FA_PLAN_GAPS_ARE_PADDING) &&
+                  (f32_numel % 2 == 0 || out_elem == FA_ELEM_F32) &&
                   covers_with_padding(s32, f32_numel, 128) &&
                   covers_with_padding(s64, i64_numel, 1);
   std::vector<Tile> tiles;
@@ -1513,12 +1520,42 @@ int fa_plan_create_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel, cons
   const int rc = check_elem(elem, &tile_elems, "fa_plan_create_elem");
   if (rc) return rc;
   return plan_create_h16(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
-                         elem, out);
+                         elem, elem, out);
+}
+
+// A mixed plan (elem 16-bit, out_elem FA_ELEM_F32): the 16-bit plan's table,
+// reduced by the wide-store instances of the 16-bit kernels into an fp32
+// bucket at the same element offsets, broadcast by the narrowing kernel.
+int fa_plan_create_elem_out(const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                            const fa_seg* seg64, int nseg64, int64_t i64_numel, int tile_elems,
+                            unsigned flags, int elem, int out_elem, fa_plan** out) {
+  if (out_elem == elem)
+    return fa_plan_create_elem(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems,
+                               flags, elem, out);
+  if (!out) return set_err(FA_E_INVAL, "fa_plan_create_elem_out: out is NULL");
+  *out = nullptr;
+  if (!((elem == FA_ELEM_F16 || elem == FA_ELEM_BF16) && out_elem == FA_ELEM_F32))
+    return set_err(FA_E_INVAL, "fa_plan_create_elem_out: out_elem must equal elem, or be "
+                               "FA_ELEM_F32 over FA_ELEM_F16 / FA_ELEM_BF16 clients (got elem %d, "
+                               "out_elem %d)", elem, out_elem);
+  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
+    return set_err(FA_E_INVAL, "fa_plan_create_elem_out: unknown flag bits 0x%x",
+                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
+  if (f32_numel < 0 || i64_numel < 0) return set_err(FA_E_INVAL, "negative bucket size");
+  const int rc = check_elem(elem, &tile_elems, "fa_plan_create_elem_out");
+  if (rc) return rc;
+  return plan_create_h16(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
+                         elem, out_elem, out);
 }
 
 int fa_plan_elem(const fa_plan* plan) {
   if (!plan) return set_err(FA_E_INVAL, "fa_plan_elem: plan is NULL");
   return plan->elem;
+}
+
+int fa_plan_out_elem(const fa_plan* plan) {
+  if (!plan) return set_err(FA_E_INVAL, "fa_plan_out_elem: plan is NULL");
+  return plan->out_elem;
 }
 
 int fa_plan_create(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
@@ -2130,6 +2167,9 @@ void launch_bcast2(const fa_plan* plan, ReduceArgs& a, int ntiles, uint32_t grou
 hipError_t launch_bcast(const fa_plan* plan, ReduceArgs& a, int n, int ntiles, hipStream_t st) {
   a.flags |= FA_F_BCAST;
   if (n <= 0) return hipSuccess;
+  if (plan->elem != plan->out_elem)  // a mixed plan: fp32 result -> 16-bit clients
+    return fa_h16::bcast_narrow(a, n, plan->elem, plan->has32 ? plan->info.f32_numel : 0,
+                                plan->has64 ? plan->info.i64_numel : 0, st);
   const uint32_t groups = (uint32_t)((n + kBcastGroupMax - 1) / kBcastGroupMax);
   const uint32_t gsize = (uint32_t)((n + groups - 1) / groups);
   // grids stay below 2^32 blocks: n clients of >= 4 KB parts would outgrow
@@ -2320,8 +2360,9 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
     return set_err(FA_E_INVAL, "fa_reduce: FA_F_SUM_ONLY is not defined for a 16-bit plan (the "
                                "ordered fp32 sum has no 16-bit slot to go to)");
   if (h16 && (flags & (FA_F_BCAST | FA_F_BCAST_ONLY)) && !plan->flat_bcast)
-    return set_err(FA_E_INVAL, "fa_reduce: a 16-bit plan broadcasts the bucket's bytes flat and "
-                               "needs FA_PLAN_GAPS_ARE_PADDING with full coverage");
+    return set_err(FA_E_INVAL, "fa_reduce: a 16-bit plan broadcasts the bucket's bytes flat (a "
+                               "mixed plan: narrows the whole fp32 bucket) and needs "
+                               "FA_PLAN_GAPS_ARE_PADDING with full coverage");
   const fa_plan_info& in = plan->info;
   if (plan->info.ntiles == 0) return FA_OK;
   ReduceArgs a;
@@ -2453,7 +2494,8 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
     a.ntiles = plan->nt_dev;
     const bool bc = (flags & FA_F_BCAST) != 0;
     a.flags &= ~FA_F_BCAST;
-    hipError_t e = fa_h16::launch(a, plan->nt_dev, plan->elem, plan->vec_u, weights != nullptr, st);
+    hipError_t e = fa_h16::launch(a, plan->nt_dev, plan->elem, plan->vec_u, weights != nullptr,
+                                  plan->out_elem == FA_ELEM_F32, st);
     if (e == hipSuccess && bc) e = launch_bcast(plan, a, n, plan->nt_dev, st);
     if (table) {
       hipError_t e2 = hipFreeAsync(table, st);

@@ -1,6 +1,7 @@
 // h16.h — launcher of the 16-bit reduce kernels (fedagg_h16.hip), called by
 // fedagg.hip's fa_reduce_tab for plans whose floating bucket holds fp16 or
-// bf16 elements (fa_plan_create_elem).
+// bf16 elements (fa_plan_create_elem), and of the narrowing broadcast of a
+// mixed plan (fa_plan_create_elem_out: fp32 result, 16-bit clients).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,16 @@ constexpr int kDefaultU = 1;                // 2048-element tiles: measured, DES
 
 // One workgroup per tile of the table in `a` (packed scalar tiles first).
 // `a.c32[]` / `a.tab32[]` / `a.out32` carry the 16-bit bucket pointers.
-hipError_t launch(const fa_k::ReduceArgs& a, int ntiles, int elem, int u, bool weighted,
+// `wide`: a.out32 is an fp32 bucket at the same element offsets and takes the
+// fp32 mean unrounded (a mixed plan).
+hipError_t launch(const fa_k::ReduceArgs& a, int ntiles, int elem, int u, bool weighted, bool wide,
                   hipStream_t st);
+
+// Clients per workgroup of the narrowing broadcast (fedagg.hip kBcastGroupMax).
+constexpr int kBcastGroup = 24;
+// a.out32's fp32 bucket over [0, f32_numel) rounded to nearest-even into every
+// client's 16-bit bucket (a.c32[] / a.tab32[]), a.out64's i64_numel elements
+// copied into every int64 bucket; either count may be 0.
+hipError_t bcast_narrow(const fa_k::ReduceArgs& a, int n, int elem, int64_t f32_numel,
+                        int64_t i64_numel, hipStream_t st);
 }  // namespace fa_h16

@@ -15,6 +15,13 @@ the floating bucket then has that dtype, every key is a zero-copy view
 kernels reduce it in place (csrc/fedagg_h16.hip).  Any other mix of dtypes
 keeps the fp32 bucket with per-call staging (kind ``packf``).
 
+An fp32 master global over such clients takes the master layout
+(``master16=True``): its own fp32 keys, zero-copy (kind ``f32``), each on the
+16-bit layout's 128-ELEMENT boundary, so every element offset, ``f32_numel``
+and the int64 offsets equal those of the clients' native 16-bit layout of the
+same keys and one tile table (a mixed plan, fa_plan_create_elem_out) serves
+the fp32 result bucket and the 16-bit client buckets.
+
 The layout fixes key order = ``global_model.state_dict()`` order, which is the
 order the reference iterates (train_fedavg.py:144) — it does not change the
 per-element arithmetic, only where each key lives.  The same layout object is
@@ -82,16 +89,25 @@ class BucketLayout:
     """Key → (bucket, offset) map plus the fa_seg tables for the kernel."""
 
     def __init__(self, entries: Sequence[Tuple[str, Sequence[int], object]],
-                 aliases: Optional[Dict[str, str]] = None, native16: bool = False):
+                 aliases: Optional[Dict[str, str]] = None, native16: bool = False,
+                 master16: bool = False):
         aliases = dict(aliases or {})
         entries = list(entries)
+        if master16:
+            if native16:
+                raise ValueError("a layout is native16 or master16, not both")
+            bad = [k for k, _, dt in entries
+                   if dtype_of(dt) not in (torch.float32, torch.int64)]
+            if bad:
+                raise TypeError(f"master layout: key {bad[0]!r} is neither float32 nor int64")
+        self.master16 = bool(master16)
         self.slots: List[Slot] = []
         self.by_key: Dict[str, Slot] = {}
         # the floating bucket's dtype: fp32, or with native16 the one 16-bit
         # dtype of every non-int64 key
         h16 = native16_dtype(dt for _, _, dt in entries) if native16 else None
         self.float_dtype = h16 if h16 is not None else torch.float32
-        align = ALIGN_H16 if h16 is not None else ALIGN_F32
+        align = ALIGN_H16 if (h16 is not None or master16) else ALIGN_F32
         off32 = 0
         off64 = 0
         for key, shape, dt in entries:
@@ -127,6 +143,8 @@ class BucketLayout:
         self.signature = tuple((s.key, s.shape, str(s.dtype), s.alias_of) for s in self.slots)
         if h16 is not None:   # the same keys laid out in an fp32 bucket are another layout
             self.signature += (("<native16>", (), str(h16), None),)
+        if master16:          # fp32 keys at the 16-bit layout's element offsets: a third one
+            self.signature += (("<master16>", (), str(torch.float32), None),)
         self.keys = [s.key for s in self.slots]
 
     # ---------------------------------------------------------- builders --
@@ -135,7 +153,8 @@ class BucketLayout:
         return cls([(e["key"], e["shape"], e["dtype"]) for e in manifest["keys"]])
 
     @classmethod
-    def from_state_dict(cls, sd, native16: bool = False) -> "BucketLayout":
+    def from_state_dict(cls, sd, native16: bool = False,
+                        master16: bool = False) -> "BucketLayout":
         entries, aliases, seen = [], {}, {}
         for k, v in sd.items():
             if not isinstance(v, torch.Tensor):
@@ -146,7 +165,7 @@ class BucketLayout:
             else:
                 seen[ident] = k
             entries.append((k, tuple(v.shape), v.dtype))
-        return cls(entries, aliases, native16)
+        return cls(entries, aliases, native16, master16)
 
     # ----------------------------------------------------------- queries --
     @property

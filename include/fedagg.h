@@ -159,8 +159,37 @@ int fa_plan_create_elem(const fa_seg *seg32, int nseg32, int64_t f32_numel,
                         const fa_seg *seg64, int nseg64, int64_t i64_numel,
                         int tile_elems, unsigned flags, int elem,
                         fa_plan **out);
-/* The plan's element type (FA_ELEM_*), < 0 on error. */
+/* The plan's element type (FA_ELEM_*), < 0 on error.  On a mixed plan
+ * (below) the clients' type. */
 int fa_plan_elem(const fa_plan *plan);
+
+/* ---- element type of the result bucket (a property of the plan too) -------
+ * The round of an fp32 master global over 16-bit clients: the reference's
+ * stack([c[k].float() ...]).mean(0) stored unrounded into the global's fp32
+ * key, then load_state_dict's copy_ rounding it to nearest-even into each
+ * client's 16-bit key.
+ * out_elem == elem: fa_plan_create_elem exactly.
+ * elem FA_ELEM_F16 / FA_ELEM_BF16 with out_elem FA_ELEM_F32: a mixed plan.
+ *   Offsets, counts, f32_numel and tile_elems are in elements, as on a 16-bit
+ *   plan (the same tile table).  fa_reduce / fa_reduce_tab: c32[i] are the
+ *   clients' 16-bit buckets; out32 is an fp32 bucket of f32_numel floats (16-B
+ *   aligned) that takes the fp32 mean (or ordered weighted sum) unrounded at
+ *   the same element offsets.  FA_F_BCAST_ONLY rounds out32 over
+ *   [0, f32_numel) into every client's 16-bit bucket (padding included) and
+ *   copies the int64 bucket; FA_F_BCAST is the reduce, then that broadcast.
+ *   The broadcast needs FA_PLAN_GAPS_ARE_PADDING and segments that cover the
+ *   bucket (no gap of >= 128 elements; any f32_numel) and is refused with
+ *   nothing written otherwise.  FA_F_SUM_ONLY and fa_reduce_chain are refused
+ *   as on a 16-bit plan.  fa_plan_launch_shape / _form answer as for a 16-bit
+ *   plan.
+ * Every other pair (an fp32 elem with a 16-bit out_elem, fp16 <-> bf16) is
+ * FA_E_INVAL. */
+int fa_plan_create_elem_out(const fa_seg *seg32, int nseg32, int64_t f32_numel,
+                            const fa_seg *seg64, int nseg64, int64_t i64_numel,
+                            int tile_elems, unsigned flags, int elem,
+                            int out_elem, fa_plan **out);
+/* The plan's result element type (FA_ELEM_*), < 0 on error. */
+int fa_plan_out_elem(const fa_plan *plan);
 
 /* Host-only tile table of a layout (no device, no allocation): for tests and
  * inspection.  kind: 0 fp32 cascade (16-B vectors), 1 fp32 cascade (scalar),
