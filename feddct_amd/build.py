@@ -10,10 +10,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # in parallel (one unit held them all: 5 minutes of device compilation)
 SRCS = [os.path.join(HERE, "csrc", f) for f in
         ("fedagg.hip", "fedagg_k1.hip", "fedagg_k2.hip", "fedagg_k2w.hip", "fedagg_k4.hip",
-         "fedagg_h16.hip", "prox.hip")]
-HEADERS = [os.path.join(HERE, "csrc", "common.h"), os.path.join(HERE, "csrc", "reduce_impl.h"),
-           os.path.join(HERE, "csrc", "h16.h"),
-           os.path.join(HERE, "..", "include", "fedagg.h")]
+         "fedagg_h16.hip", "prox.hip", "plan_host.cpp")]
+HEADERS = [os.path.join(HERE, "csrc", h) for h in
+           ("common.h", "err.h", "tiles.h", "plan_host.h", "reduce_impl.h", "h16.h")] + \
+          [os.path.join(HERE, "..", "include", "fedagg.h")]
 DEPS = SRCS + HEADERS
 OUT = os.path.join(HERE, "libfedagg.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
@@ -32,7 +32,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 # public ABI, so the core library does not depend on RCCL.  librccl.so.1
 # resolves to the copy torch has already loaded (same soname).
 COMM_SRC = os.path.join(HERE, "csrc", "fedcomm.hip")
-COMM_DEPS = [COMM_SRC, os.path.join(HERE, "csrc", "common.h"),
+COMM_DEPS = [COMM_SRC, os.path.join(HERE, "csrc", "common.h"), os.path.join(HERE, "csrc", "err.h"),
              os.path.join(HERE, "..", "include", "fedagg.h"),
              os.path.join(HERE, "..", "include", "fedagg_comm.h")]
 COMM_OUT = os.path.join(HERE, "libfedagg_comm.so")
@@ -82,6 +82,9 @@ def _compile_units(srcs, flags, jobs=None, force=False):
     os.makedirs(objdir, exist_ok=True)
     jobs = jobs or min(len(srcs), int(os.environ.get("MAX_JOBS", "0")) or os.cpu_count() or 4, 16)
     cflags = [f for f in flags if f not in ("-shared",)]
+    # a .cpp unit holds no device code (plan_host.cpp: the planners): plain
+    # C++, no offload arch; -D overrides reach it like every other unit
+    host = ["-x", "c++"] + [f for f in cflags if not f.startswith("--offload-arch")]
     objs, procs = [], []
     for src in srcs:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
@@ -90,7 +93,8 @@ def _compile_units(srcs, flags, jobs=None, force=False):
             continue
         while len([p for p in procs if p.poll() is None]) >= jobs:
             procs[[p.poll() is None for p in procs].index(True)].wait()
-        procs.append(subprocess.Popen([HIPCC, *cflags, "-c", "-o", obj, src]))
+        uflags = host if src.endswith(".cpp") else cflags
+        procs.append(subprocess.Popen([HIPCC, *uflags, "-c", "-o", obj, src]))
     bad = [p.args[-1] for p in procs if p.wait() != 0]
     if bad:
         raise subprocess.CalledProcessError(1, f"hipcc -c {bad}")

@@ -3,11 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fedagg.h"
-
-namespace fa {
-// thread-local last-error message (fa_last_error); returns code
-int set_err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-}  // namespace fa
+#include "err.h"
 
 #define FA_HIP_TRY(expr)                                                        \
   do {                                                                          \

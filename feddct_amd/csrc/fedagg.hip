@@ -11,6 +11,9 @@
 // on the host into a tile table; one 256-thread workgroup streams one tile:
 // per client, one coalesced 16-B load per lane per vector (1 KiB per wave
 // instruction), loads for a batch of clients issued before their adds.
+// The planners that cut the tables and the rules that pick a call's table
+// and kernel form are plain host code (plan_host.cpp); this unit holds the
+// kernels, the occupancy queries, the uploads, the C ABI and the launches.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 // (no fast-math, no FTZ: the sum must be IEEE round-to-nearest-even, no FMA).
@@ -24,12 +27,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
-#include <queue>
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "plan_host.h"
 
 #define FA_VERSION_STR "fedagg 0.1.0 gfx950"
 
@@ -813,33 +817,24 @@ int grid_for(int64_t work, int per_block) {
 
 }  // namespace
 
-struct fa_plan {
-  int device = 0;
+// The plan's host summary — device, flags, vec_u, and the device tables' own
+// counts nt / ns / nt_alt / ns_alt / bal[] (their scalar tiles are packed,
+// r03, K_SCALAR_PACKED; info.* keep the host view of the layout's tiles) —
+// is the launch rules' input (fa_host::PlanShape); the device pointers are
+// held here.
+struct fa_plan : fa_host::PlanShape {
   Tile* d_tiles = nullptr;
   fa_plan_info info{};
-  int vec_u = kDefaultU;
   // auto plans (tile_elems == 0) also carry a 1024-float table, used for
-  // unweighted reductions over >= 64 clients (tools/tune.py sweep)
+  // unweighted reductions over 129..255 clients (fa_host::select_launch)
   Tile* d_tiles_alt = nullptr;
-  int ntiles_alt = 0;
-  int nscalar_alt = 0;
-  // the device tables' own counts: their scalar tiles are packed (r03,
-  // K_SCALAR_PACKED; info.* keep the host view of the layout's tiles)
-  int nt_dev = 0, ns_dev = 0, nt_alt_dev = 0, ns_alt_dev = 0;
   int64_t* d_sidx = nullptr;  // packed scalar columns: (element << 4) | kind, -1 unused
   int64_t sidx_alt_off = 0;   // the alt table's region of d_sidx
-  // balanced tables (r03): the vector tiles re-cut so that packed + vector
-  // tiles fill whole rounds of `slots` resident workgroups (balance_vec);
-  // their packed tiles are the main table's (same scalar index region)
-  struct BalTable {
-    int u = 0, slots = 0;
-    int batch = 16;  // clients per load batch of the kernel it was cut for
-    Tile* d = nullptr;
-    int nt = 0;
-    bool alt = false;  // cut from the alt (1024-float) table: its scalar index region
-  };
-  std::vector<BalTable> bal;
-  unsigned flags = 0;
+  // balanced tables (r03), bal[i]'s tiles: the vector tiles re-cut so that
+  // packed + vector tiles fill whole rounds of `slots` resident workgroups
+  // (balance_vec); their packed tiles are the main table's (same scalar
+  // index region)
+  std::vector<Tile*> d_bal;
   bool has32 = false;  // the tile table touches the fp32 bucket
   bool has64 = false;  // ... the int64 bucket
   // element type of the floating bucket (fa_plan_create_elem).  A 16-bit
@@ -863,187 +858,10 @@ struct fa_plan {
 
 namespace {
 void set_kinds(fa_plan* p, const std::vector<Tile>& t) {
-  for (const Tile& x : t) {
-    if (x.kind >= K_I64_CASC) p->has64 = true;
-    else p->has32 = true;
-  }
-}
-}  // namespace
-
-namespace {
-
-inline int64_t body_len(int64_t M) {
-  if (M >= 8) return (M / 32) * 32;
-  if (M >= 2) return (M / 4) * 4;
-  return 0;
-}
-
-int check_segs(const fa_seg* s, int ns, int64_t numel, const char* what,
-               std::vector<fa_seg>* sorted) {
-  if (ns < 0 || (ns > 0 && !s)) return set_err(FA_E_INVAL, "%s: bad segment array", what);
-  sorted->assign(s, s + ns);
-  std::stable_sort(sorted->begin(), sorted->end(),
-                   [](const fa_seg& x, const fa_seg& y) { return x.offset < y.offset; });
-  int64_t end = 0;
-  for (const fa_seg& g : *sorted) {
-    if (g.offset < 0 || g.numel < 0 || g.offset + g.numel > numel)
-      return set_err(FA_E_INVAL, "%s: segment [%lld,+%lld) outside bucket of %lld", what,
-                     (long long)g.offset, (long long)g.numel, (long long)numel);
-    if (g.numel > 0 && g.offset < end)
-      return set_err(FA_E_INVAL, "%s: overlapping segments at %lld", what, (long long)g.offset);
-    if (g.numel > 0) end = g.offset + g.numel;
-  }
-  return FA_OK;
-}
-
-// May the broadcast copy the buckets flat?  Only when the caller declared the
-// gaps padding (FA_PLAN_GAPS_ARE_PADDING) AND the segments, with that
-// padding, cover the whole bucket: no gap (leading, between, trailing) of
-// `pad` elements or more, i.e. no room for a key the plan does not own.  A
-// plan over some of a layout's keys (a column chunk) keeps the tile-table
-// broadcast, which writes its own tiles only.
-bool covers_with_padding(const std::vector<fa_seg>& s, int64_t numel, int64_t pad) {
-  int64_t pos = 0;
-  for (const fa_seg& g : s) {
-    if (g.numel == 0) continue;
-    if (g.offset - pos >= pad) return false;
-    pos = g.offset + g.numel;
-  }
-  return numel - pos < pad;
-}
-
-bool flat_bcast_ok(unsigned flags, const std::vector<fa_seg>& s32, int64_t f32_numel,
-                   const std::vector<fa_seg>& s64, int64_t i64_numel) {
-  return (flags & FA_PLAN_GAPS_ARE_PADDING) && covers_with_padding(s32, f32_numel, 64) &&
-         covers_with_padding(s64, i64_numel, 1);
-}
-
-// Every element belongs to at most one tile: two tiles over one element would
-// race two summation orders (and two stores) into the same output.
-int check_disjoint(std::vector<Tile> t, const char* who) {
-  std::sort(t.begin(), t.end(), [](const Tile& x, const Tile& y) {
-    const bool x64 = kind_is64(x.kind), y64 = kind_is64(y.kind);
-    return x64 != y64 ? y64 : x.start < y.start;
-  });
-  for (size_t i = 1; i < t.size(); ++i)
-    if (kind_is64(t[i - 1].kind) == kind_is64(t[i].kind) &&
-        t[i - 1].start + t[i - 1].count > t[i].start)
-      return set_err(FA_E_INVAL, "%s: tiles overlap at %s element %lld", who,
-                     kind_is64(t[i].kind) ? "int64" : "fp32", (long long)t[i].start);
-  return FA_OK;
-}
-
-void push_scalar(std::vector<Tile>* t, int64_t start, int64_t count, int kind) {
-  for (int64_t c = 0; c < count; c += kBlock)
-    t->push_back(Tile{start + c, (int32_t)std::min<int64_t>(kBlock, count - c), kind});
-}
-
-// valign: elements per 16-B vector (4 fp32, 8 fp16 / bf16): a cascade body is
-// vectorised when it starts and ends on that boundary.
-int build_tiles(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, int tile_elems,
-                unsigned flags, std::vector<Tile>* out, fa_plan_info* info, int valign = 4) {
-  std::vector<Tile> vec, tail;
-  // Maximal runs of cascade-order elements, 16-B aligned (vectorisable).
-  int64_t run_s = -1, run_e = -1;
-  auto flush = [&]() {
-    if (run_s < 0) return;
-    for (int64_t c = run_s; c < run_e; c += tile_elems)
-      vec.push_back(Tile{c, (int32_t)std::min<int64_t>(tile_elems, run_e - c), K_F32_VEC});
-    info->cascade_elems += run_e - run_s;
-    run_s = run_e = -1;
-  };
-  for (const fa_seg& g : s32) {
-    const int64_t M = g.numel;
-    if (M == 0) continue;
-    if (M == 1) {
-      // the scalar breaks the run: a later aligned segment must not extend
-      // the open vector run across this element (it would be covered twice)
-      flush();
-      push_scalar(&tail, g.offset, 1, K_F32_INNER);
-      info->tail_elems += 1;
-      continue;
-    }
-    const int64_t b = body_len(M);
-    if (b > 0) {
-      if (g.offset % valign == 0 && b % valign == 0) {
-        const bool extend = run_s >= 0 && (run_e == g.offset ||
-                                           ((flags & FA_PLAN_GAPS_ARE_PADDING) && run_e <= g.offset));
-        if (!extend) flush();
-        if (run_s < 0) run_s = g.offset;
-        run_e = g.offset + b;
-      } else {
-        flush();
-        push_scalar(&tail, g.offset, b, K_F32_CASC_S);
-        info->tail_elems += b;
-      }
-    }
-    if (b < M) {
-      flush();  // the tail breaks the run
-      push_scalar(&tail, g.offset + b, M - b, K_F32_ILP4);
-      info->tail_elems += M - b;
-    }
-  }
-  flush();
-  for (const fa_seg& g : s64) {
-    const int64_t M = g.numel;
-    if (M == 0) continue;
-    if (M == 1) { push_scalar(&tail, g.offset, 1, K_I64_INNER); continue; }
-    const int64_t b = body_len(M);
-    if (b) push_scalar(&tail, g.offset, b, K_I64_CASC);
-    if (b < M) push_scalar(&tail, g.offset + b, M - b, K_I64_ILP4);
-  }
-  std::vector<Tile> all(vec);
-  all.insert(all.end(), tail.begin(), tail.end());
-  const int rc = check_disjoint(all, "tile planner");
-  if (rc) return rc;
-  // Scalar tiles first: their few long-latency workgroups start early and
-  // finish under the vector stream instead of trailing it.
-  out->clear();
-  out->insert(out->end(), tail.begin(), tail.end());
-  out->insert(out->end(), vec.begin(), vec.end());
-  info->ntiles = (int32_t)out->size();
-  info->ntiles_cascade = (int32_t)vec.size();
-  info->ntiles_tail = (int32_t)tail.size();
-  return FA_OK;
+  for (const Tile& x : t) (kind_is64(x.kind) ? p->has64 : p->has32) = true;
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-// Clients per load batch of the reduce kernel a call runs (launch_reduce).
-// r06: the 16-client kernels (three workgroups per CU) from 12 clients, with
-// the client loop (pipe_rule): same process (profiles/r06_ab_lib_mid_n.jsonl)
-// N = 12 / 14 / 16 -1.8 / -2.7 / -0.3 %, weighted N = 12 -1.4 / -1.5 % (C10 /
-// C100); at N = 10 +1.0 %, so below 12 the 8-client kernels stay.
-#ifndef FA_B16_MIN
-#define FA_B16_MIN 12
-#endif
-int pick_batch(int n, int vec_u, unsigned pflags) {
-  const int b = (pflags & FA_PLAN_TUNE_BATCH8)    ? 8
-                : (pflags & FA_PLAN_TUNE_BATCH16) ? 16 : (n < FA_B16_MIN ? 8 : 16);
-  return (vec_u == 4 && b == 16) ? 8 : b;  // no 16-client kernels at U = 4
-}
-
-// ------------------------------------------------------ balanced tables --
-// One workgroup per tile: a launch of T equal tiles over `slots` resident
-// workgroups (CUs x workgroups per CU) runs ceil(T / slots) rounds, and a
-// part-filled round costs nearly a whole one while the launch is only one or
-// two rounds long — measured r03 on one fp32 tensor of T x 2048 floats
-// (tools/archive/exp_batch_cross.py, profiles/r03_exp_batch_cross*.jsonl), N = 20,
-// 16-client kernel on 768 slots: 384 tiles 16.1 us, re-cut to 768 13.4 us;
-// 768 tiles 22.7 us; 1,024 tiles 33.5 us, on the 8-client kernel's 1,280
-// slots (one round) 28.3 us.  Past two rounds the tail is a small share and
-// a re-cut (smaller, partial tiles) costs more than it saves: cfg4 weighted
-// 144.2 vs 142.0 us, cfg5 185.5 vs 181.4 us, cfg3 43.7 vs 43.5 us re-cut vs
-// plain (profiles/r03_exp_tune_balance.jsonl).  So a call of N >= 16
-// clients whose plain table (a) part-fills ONE round of the 16-client kernel
-// runs a table re-cut to fill it, (b) needs two rounds of the 16-client
-// kernel but one of the 8-client kernel runs the 8-client kernel (resnet110sl
-// sf4 N = 25, 923 tiles: 23.0 vs 26.3 us plain, 23.9 re-cut), (c) spills a
-// few tiles past its last full round: the tail split below (split_tail), and
-// (d) runs the plain table otherwise.  N < 16 (8-client kernel already) always runs
-// plain: at N = 5 a re-cut is no gain (384 tiles 7.8 vs 9.0 us).
-constexpr double kKeepFill = 0.97;  // the round at least this full: keep the plain table
-constexpr int64_t kMinTile = 256;   // never cut vector tiles below this (elements)
 
 // Resident workgroups of the reduce kernel (U, B, deep, weighted) on device
 // `dev`, queried once per process (0: unknown -> the plain table).
@@ -1071,130 +889,6 @@ int kernel_slots(int dev, int u, int b, bool deep, bool w) {
   return slots;
 }
 
-// The slot count a plain (non-chain) reduce call runs on; 0 for a plan that
-// launches its tiles as given (FA_PLAN_TUNE_NO_BALANCE).
-int call_slots(int dev, int n, int vec_u, bool w, unsigned pflags) {
-  if (pflags & FA_PLAN_TUNE_NO_BALANCE) return 0;
-  return kernel_slots(dev, vec_u, pick_batch(n, vec_u, pflags), n >= 256, w);
-}
-
-// Case (b) above: the batch a plain call of n clients runs with, given the
-// plain table's tile count — 8 instead of 16 when that turns two rounds into
-// one.  Explicit batch tuning flags and grid-shaping flags keep their batch.
-int round_batch(int dev, int n, int vec_u, bool w, unsigned pflags, int ntiles) {
-  const int b = pick_batch(n, vec_u, pflags);
-  if (b != 16 || (pflags & (FA_PLAN_TUNE_BATCH16 | FA_PLAN_TUNE_NO_BALANCE))) return b;
-  const int s16 = kernel_slots(dev, vec_u, 16, n >= 256, w);
-  const int s8 = kernel_slots(dev, vec_u, 8, n >= 256, w);
-  return (s16 > 0 && s8 > s16 && ntiles > s16 && ntiles <= s8) ? 8 : 16;
-}
-
-// A multi-round launch whose last round holds only r << slots tiles (r03
-// session 4, tools/archive/exp_round_quant.py, profiles/r03_exp_round_quant.jsonl):
-// those r tiles run alone, latency-bound, ~7-8 us after the last full round
-// at N = 20 — cfg2's layout plus 16 / 18 / 25 extra 2048-float tiles (r = 1
-// / 3 / 10 past 7 rounds of 768) reads 139.0 / 142.3 / 143.9 us against
-// 136.3 us at 6.99 rounds, while 300 extra tiles cost only 146.4 us.  So the
-// LAST slots - r vector tiles are split in halves (64-element lines): the
-// table then fills exactly k rounds, its last round made of half tiles, and
-// every earlier tile keeps the full width (re-cutting the whole table
-// instead was slower, see above).  Same process, weighted, split vs plain
-// (profiles/r03_exp_round_quant_tail_split*.jsonl): r = 10 137.9 vs 143.8
-// us, r = 85 139.5 vs 144.0, r = 135 141.5 vs 144.8, r = 285 144.8 vs 146.3,
-// r = 335 145.4 vs 147.6 — a gain at every r measured, up to 0.44 slots,
-// so it is applied for 0 < r <= 0.44 slots (r03 applied it up to
-// slots / 2, past the measured range).  A tile too small to halve (< 2 *
-// kMinTile / 2 elements: ragged ends of runs) is left whole, so such a table
-// may end up a few tiles short of exactly k rounds; the bits never change.
-constexpr int64_t kTailMaxPct = 44;
-std::vector<Tile> split_tail(const std::vector<Tile>& tiles, int64_t r, int slots) {
-  if (r <= 0 || r * 100 > kTailMaxPct * (int64_t)slots) return {};
-  std::vector<Tile> vec;
-  for (const Tile& x : tiles)
-    if (x.kind == K_F32_VEC) vec.push_back(x);
-  const int64_t m = slots - r;  // tiles to split
-  if ((int64_t)vec.size() < m) return {};
-  std::vector<Tile> out;
-  out.reserve(vec.size() + (size_t)m);
-  const size_t first = vec.size() - (size_t)m;
-  for (size_t i = 0; i < vec.size(); ++i) {
-    const Tile& x = vec[i];
-    const int64_t h = ((int64_t)x.count / 2) & ~(int64_t)63;
-    if (i < first || h < kMinTile / 2) {
-      out.push_back(x);
-      continue;
-    }
-    out.push_back(Tile{x.start, (int32_t)h, K_F32_VEC});
-    out.push_back(Tile{x.start + h, (int32_t)(x.count - h), K_F32_VEC});
-  }
-  return out;
-}
-
-// The vector tiles of `tiles` (cut at cmax elements), re-cut for `slots`:
-// only when they part-fill a single round (k = 1: slots - nscalar vector tiles),
-// handed out run by run (a run = adjacent vector tiles) to the run whose
-// tiles are largest, boundaries on 64-element (256 B) lines, no tile above
-// cmax or (when split further) below kMinTile.  Empty: keep the plain table.
-std::vector<Tile> balance_vec(const std::vector<Tile>& tiles, int cmax, int nscalar, int slots,
-                              bool tail_only = false) {
-  std::vector<std::pair<int64_t, int64_t>> runs;  // [start, end)
-  int64_t t0 = 0;
-  for (const Tile& x : tiles) {
-    if (x.kind != K_F32_VEC) continue;
-    ++t0;
-    if (!runs.empty() && runs.back().second == x.start) runs.back().second += x.count;
-    else runs.emplace_back(x.start, x.start + x.count);
-  }
-  if (t0 == 0 || slots <= 0) return {};
-  const int64_t have = t0 + nscalar;
-  const int64_t k = (have + slots - 1) / slots;
-  if (k > 1) return split_tail(tiles, have - (k - 1) * slots, slots);
-  if (tail_only || (double)have >= kKeepFill * (double)(k * slots)) return {};
-  const int64_t target = k * slots - nscalar;
-  std::vector<int64_t> m(runs.size());
-  std::priority_queue<std::pair<double, size_t>> pq;  // (tile size, run), largest first
-  int64_t total = 0;
-  for (size_t r = 0; r < runs.size(); ++r) {
-    const int64_t len = runs[r].second - runs[r].first;
-    m[r] = (len + cmax - 1) / cmax;
-    total += m[r];
-    pq.emplace((double)len / (double)m[r], r);
-  }
-  while (total < target && !pq.empty()) {
-    const size_t r = pq.top().second;
-    pq.pop();
-    const int64_t len = runs[r].second - runs[r].first;
-    if ((double)len / (double)(m[r] + 1) < (double)kMinTile) break;  // every run is as small
-    ++m[r];
-    ++total;
-    pq.emplace((double)len / (double)m[r], r);
-  }
-  if (total == t0) return {};
-  std::vector<Tile> out;
-  out.reserve((size_t)total + 16);
-  for (size_t r = 0; r < runs.size(); ++r) {
-    const int64_t s = runs[r].first, e = runs[r].second, len = e - s;
-    for (int64_t mm = m[r];; ++mm) {
-      const size_t mark = out.size();
-      int64_t prev = s;
-      bool ok = true;
-      for (int64_t j = 1; j <= mm; ++j) {
-        const int64_t b = j == mm ? e : ((s + j * len / mm) & ~(int64_t)63);
-        if (b <= prev) continue;  // (a boundary rounded onto the previous one)
-        if (b - prev > cmax) {
-          ok = false;
-          break;
-        }
-        out.push_back(Tile{prev, (int32_t)(b - prev), K_F32_VEC});
-        prev = b;
-      }
-      if (ok) break;
-      out.resize(mark);  // rounding pushed a tile past cmax: one more tile
-    }
-  }
-  return out;
-}
-
 hipError_t launch_chain(const ReduceArgs& a, int ntiles, int vec_u, hipStream_t st) {
   const bool deep = a.n_total >= 256;
   const bool w = a.flags & 0x100u;
@@ -1205,15 +899,15 @@ hipError_t launch_chain(const ReduceArgs& a, int ntiles, int vec_u, hipStream_t 
 }
 
 
-hipError_t launch_reduce(const ReduceArgs& a, int ntiles, int vec_u, unsigned pflags,
-                         hipStream_t st, int batch = 0, int pipe = 0) {
+// batch, pipe: the launch rules' choice (fa_host::select_launch)
+hipError_t launch_reduce(const ReduceArgs& a, int ntiles, int vec_u, hipStream_t st, int b,
+                         int pipe) {
   // DEEP (n >= 256): cascade levels 2-3 and the constant-space table loads.
   // Weighted reductions take the mean's 16-client batches too since the
   // batch's weights are read once up front (r02 sweep, same box: weighted
   // U2xB16 140.5 us vs U2xB8 143.3 us, unweighted 143.0 us).
   const bool deep = a.n >= 256;
   const bool w = a.flags & 0x100u;  // internal: weighted
-  const int b = batch > 0 ? batch : pick_batch(a.n, vec_u, pflags);
   switch (vec_u) {
     case 1: return b == 16 ? launch_u<1, 16>(a, ntiles, deep, w, 0, st)
                            : launch_u<1, 8>(a, ntiles, deep, w, 0, st);
@@ -1322,127 +1016,113 @@ hipError_t table_fill(void* dst, const std::vector<char>& host, hipStream_t st) 
 }  // namespace
 
 namespace {
-// The device form of a host tile table: its scalar tiles' columns, sorted by
-// kind (a wave then mostly runs one order), packed kPackCols per K_SCALAR_PACKED
-// tile with their entries appended to `sidx`; the vector tiles follow
-// unchanged.  *nscalar = packed tiles (they lead the table, as the scalar
-// tiles did).
-std::vector<Tile> pack_scalar(const std::vector<Tile>& t, std::vector<int64_t>* sidx,
-                              int* nscalar, unsigned flags) {
-  (void)flags;
-  const int pack = kPackCols;
-  std::vector<std::pair<int, int64_t>> cols;
-  std::vector<Tile> vec;
-  for (const Tile& x : t) {
-    if (x.kind == K_F32_VEC) {
-      vec.push_back(x);
-      continue;
-    }
-    for (int32_t c = 0; c < x.count; ++c) cols.emplace_back(x.kind, x.start + c);
+// A plan under construction: every error path frees whatever was uploaded;
+// a create path releases it into *out only on success.
+struct PlanDelete {
+  void operator()(fa_plan* p) const {
+    for (void* d : {(void*)p->d_fac, (void*)p->d_tiles, (void*)p->d_tiles_alt, (void*)p->d_sidx})
+      if (d) (void)hipFree(d);
+    for (Tile* d : p->d_bal) (void)hipFree(d);
+    delete p;
   }
-  std::stable_sort(cols.begin(), cols.end(),
-                   [](const std::pair<int, int64_t>& u, const std::pair<int, int64_t>& v) {
-                     return u.first < v.first;
-                   });
-  std::vector<Tile> out;
-  for (size_t c = 0; c < cols.size(); c += pack) {
-    const int cnt = (int)std::min<size_t>(pack, cols.size() - c);
-    out.push_back(Tile{(int64_t)sidx->size(), cnt, K_SCALAR_PACKED});
-    for (int i = 0; i < kPackCols; ++i)
-      sidx->push_back(i < cnt ? (cols[c + i].second << 4) | cols[c + i].first : -1);
-  }
-  *nscalar = (int)out.size();
-  out.insert(out.end(), vec.begin(), vec.end());
-  return out;
+};
+using PlanPtr = std::unique_ptr<fa_plan, PlanDelete>;
+
+template <class T>
+hipError_t upload(T** d, const std::vector<T>& h) {
+  if (h.empty()) return hipSuccess;
+  const hipError_t e = hipMalloc(d, h.size() * sizeof(T));
+  return e != hipSuccess ? e : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
-// Upload a CPU-order plan's device tables (main + optional alt) and the
-// shared scalar index.
+// Upload a CPU-order plan's device tables (fa_host::plan_tables: main +
+// optional alt, the shared scalar index, the balanced tables).
 hipError_t upload_tables(fa_plan* p, const std::vector<Tile>& tiles,
                          const std::vector<Tile>& alt) {
-  std::vector<int64_t> sidx;
-  const std::vector<Tile> dm = pack_scalar(tiles, &sidx, &p->ns_dev, p->flags);
-  p->nt_dev = (int)dm.size();
-  std::vector<Tile> da;
-  if (!alt.empty()) {
-    // the alt table's packed tiles index their own region of the scalar
-    // index (the kernels get its base: tile k's entries at base + k * kPackCols)
-    std::vector<int64_t> sa;
-    da = pack_scalar(alt, &sa, &p->ns_alt_dev, p->flags);
-    p->sidx_alt_off = (int64_t)sidx.size();
-    sidx.insert(sidx.end(), sa.begin(), sa.end());
-    p->nt_alt_dev = (int)da.size();
-  }
-  hipError_t e = hipSuccess;
-  if (!dm.empty()) {
-    e = hipMalloc(&p->d_tiles, dm.size() * sizeof(Tile));
-    if (e == hipSuccess)
-      e = hipMemcpy(p->d_tiles, dm.data(), dm.size() * sizeof(Tile), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !da.empty()) {
-    e = hipMalloc(&p->d_tiles_alt, da.size() * sizeof(Tile));
-    if (e == hipSuccess)
-      e = hipMemcpy(p->d_tiles_alt, da.data(), da.size() * sizeof(Tile), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !sidx.empty()) {
-    e = hipMalloc(&p->d_sidx, sidx.size() * sizeof(int64_t));
-    if (e == hipSuccess)
-      e = hipMemcpy(p->d_sidx, sidx.data(), sidx.size() * sizeof(int64_t), hipMemcpyHostToDevice);
-  }
-  // balanced tables for every slot count a call on this plan may run on
-  // (main table: the 16-client kernels, deep or not, weighted or not; the
-  // alt table: its unweighted 16-client kernels)
-  if (e != hipSuccess || (p->flags & FA_PLAN_TUNE_NO_BALANCE)) return e;
-  struct Req {
-    int u, slots, batch;
-    const std::vector<Tile>* host;
-    const std::vector<Tile>* dev;
-    int ns;
-  };
-  std::vector<Req> reqs;
-  auto want = [&](int u, int slots, int batch, const std::vector<Tile>* host,
-                  const std::vector<Tile>* dev, int ns) {
-    if (slots <= 0) return;
-    for (const Req& q : reqs)
-      if (q.u == u && q.slots == slots && q.batch == batch && q.dev == dev) return;
-    reqs.push_back(Req{u, slots, batch, host, dev, ns});
-  };
-  // the 16-client kernels' calls: the whole rule; the calls of N < 16 (the
-  // 8-client kernels): the tail split only (tools/archive/exp_tail_small_n.py: N = 5
-  // / 8 / 12, 1.1-2.9 us per launch; a one-round re-cut is no gain there)
-  for (int deep = 0; deep < 2; ++deep)
-    for (int w = 0; w < 2; ++w) {
-      if (pick_batch(16, p->vec_u, p->flags) == 16)
-        want(p->vec_u, kernel_slots(p->device, p->vec_u, 16, deep != 0, w != 0), 16, &tiles,
-             &dm, p->ns_dev);
-      const int b8 = pick_batch(8, p->vec_u, p->flags);
-      if (deep == 0)
-        want(p->vec_u, kernel_slots(p->device, p->vec_u, b8, false, w != 0), b8, &tiles, &dm,
-             p->ns_dev);
-    }
-  if (!da.empty())
-    for (int deep = 0; deep < 2; ++deep)
-      want(1, kernel_slots(p->device, 1, pick_batch(64, 1, p->flags), deep != 0, false),
-           pick_batch(64, 1, p->flags), &alt, &da, p->ns_alt_dev);
-  for (const Req& q : reqs) {
-    const std::vector<Tile> v =
-        balance_vec(*q.host, q.u * 4 * kBlock, q.ns, q.slots, q.batch < 16);
-    if (v.empty()) continue;
-    std::vector<Tile> t(q.dev->begin(), q.dev->begin() + q.ns);  // the packed tiles lead
-    t.insert(t.end(), v.begin(), v.end());
-    fa_plan::BalTable b;
-    b.u = q.u;
-    b.slots = q.slots;
-    b.batch = q.batch;
-    b.nt = (int)t.size();
-    b.alt = q.dev == &da;
-    e = hipMalloc(&b.d, t.size() * sizeof(Tile));
-    if (e == hipSuccess)
-      e = hipMemcpy(b.d, t.data(), t.size() * sizeof(Tile), hipMemcpyHostToDevice);
-    if (b.d) p->bal.push_back(b);
-    if (e != hipSuccess) return e;
+  const fa_host::HostTables h =
+      fa_host::plan_tables(tiles, alt, p->vec_u, p->flags, p->device, kernel_slots);
+  p->nt = (int)h.main.size();
+  p->ns = h.ns_main;
+  p->nt_alt = (int)h.alt.size();
+  p->ns_alt = h.ns_alt;
+  p->sidx_alt_off = h.sidx_alt_off;
+  hipError_t e = upload(&p->d_tiles, h.main);
+  if (e == hipSuccess) e = upload(&p->d_tiles_alt, h.alt);
+  if (e == hipSuccess) e = upload(&p->d_sidx, h.sidx);
+  for (const fa_host::HostTables::Bal& b : h.bal) {
+    if (e != hipSuccess) break;
+    Tile* d = nullptr;
+    e = upload(&d, b.tiles);
+    if (!d) break;
+    p->bal.push_back({b.u, b.slots, b.batch, (int)b.tiles.size(), b.alt});
+    p->d_bal.push_back(d);
   }
   return e;
+}
+
+// One body behind fa_plan_create, fa_plan_create_elem and
+// fa_plan_create_elem_out (`who`, in the messages).  A 16-bit plan (elem
+// FA_ELEM_F16 / FA_ELEM_BF16) holds the plain table only, cut at 16-B
+// vectors of 8 elements; a mixed plan (out_elem FA_ELEM_F32 over 16-bit
+// clients) is that table, reduced by the wide-store instances of the 16-bit
+// kernels into an fp32 bucket at the same element offsets and broadcast by
+// the narrowing kernel.
+int plan_create(const char* who, const char* flags_hint, const fa_seg* seg32, int nseg32,
+                int64_t f32_numel, const fa_seg* seg64, int nseg64, int64_t i64_numel,
+                int tile_elems, unsigned flags, int elem, int out_elem, fa_plan** out) {
+  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
+  *out = nullptr;
+  fa_host::Layout l;
+  int rc = fa_host::parse_layout(who, flags_hint, fa_host::kCheckSizes | fa_host::kCheckTile, seg32,
+                                 nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
+                                 elem, &l);
+  if (rc) return rc;
+  const bool h16 = elem != FA_ELEM_F32;
+  PlanPtr p(new fa_plan());
+  p->elem = elem;
+  p->out_elem = out_elem;
+  p->info = l.info;
+  p->vec_u = l.info.tile_elems / (h16 ? fa_h16::kTile : 4 * kBlock);
+  // a 16-bit plan: the plain table is the one launched
+  p->flags = h16 ? flags | FA_PLAN_TUNE_NO_BALANCE : flags;
+  p->flat_bcast = fa_host::flat_bcast_ok(flags, l, elem, out_elem);
+  std::vector<Tile> tiles, alt;
+  rc = fa_host::build_tiles(l.s32, l.s64, l.info.tile_elems, flags, &tiles, &p->info, l.valign);
+  if (rc) return rc;
+  set_kinds(p.get(), tiles);
+  if (l.autosel) {
+    fa_plan_info ia{};
+    rc = fa_host::build_tiles(l.s32, l.s64, 4 * kBlock, flags, &alt, &ia);
+    if (rc) return rc;
+  }
+  hipError_t e = hipGetDevice(&p->device);
+  if (e == hipSuccess) e = upload_tables(p.get(), tiles, alt);
+  if (e != hipSuccess)
+    return set_err(FA_E_HIP, "%s: %s", h16 ? "fa_plan_create_elem" : "fa_plan_create",
+                   hipGetErrorString(e));
+  *out = p.release();
+  return FA_OK;
+}
+
+// One body behind fa_plan_build_host and fa_plan_build_host_elem.
+int plan_build_host(const char* who, const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                    const fa_seg* seg64, int nseg64, int64_t i64_numel, int tile_elems,
+                    unsigned flags, int elem, fa_tile_desc* tiles, int cap, fa_plan_info* info) {
+  if (!info) return set_err(FA_E_INVAL, "%s: info is NULL", who);
+  fa_host::Layout l;
+  int rc = fa_host::parse_layout(who, "", fa_host::kCheckTile, seg32, nseg32, f32_numel, seg64,
+                                 nseg64, i64_numel, tile_elems, flags, elem, &l);
+  if (rc) return rc;
+  std::vector<Tile> t;
+  rc = fa_host::build_tiles(l.s32, l.s64, l.info.tile_elems, flags, &t, &l.info, l.valign);
+  if (rc) return rc;
+  *info = l.info;
+  if (tiles) {
+    if (cap < (int)t.size())
+      return set_err(FA_E_RANGE, "%s: %d tiles, capacity %d", who, (int)t.size(), cap);
+    for (size_t i = 0; i < t.size(); ++i) tiles[i] = fa_tile_desc{t[i].start, t[i].count, t[i].kind};
+  }
+  return FA_OK;
 }
 }  // namespace
 
@@ -1451,58 +1131,11 @@ extern "C" {
 const char* fa_version(void) { return FA_VERSION_STR; }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 
-// A 16-bit plan (fa_plan_create_elem, FA_ELEM_F16 / FA_ELEM_BF16): the
-// plain table of the layout cut at 16-B vectors of 8 elements; its kernels
-// (fedagg_h16.hip) take one table at every client count.
-static int check_elem(int elem, int* tile_elems, const char* who) {
-  if (elem != FA_ELEM_F32 && elem != FA_ELEM_F16 && elem != FA_ELEM_BF16)
-    return set_err(FA_E_INVAL, "%s: elem must be FA_ELEM_F32, FA_ELEM_F16 or FA_ELEM_BF16 (got %d)",
-                   who, elem);
-  if (elem == FA_ELEM_F32) return FA_OK;
-  if (*tile_elems == 0) *tile_elems = fa_h16::kDefaultU * fa_h16::kTile;
-  if (*tile_elems != fa_h16::kTile && *tile_elems != 2 * fa_h16::kTile)
-    return set_err(FA_E_INVAL, "%s: a 16-bit plan's tile_elems must be 2048 or 4096 (got %d)", who,
-                   *tile_elems);
-  return FA_OK;
-}
-
-static int plan_create_h16(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
-                           int nseg64, int64_t i64_numel, int tile_elems, unsigned flags, int elem,
-                           int out_elem, fa_plan** out) {
-  std::vector<fa_seg> s32, s64;
-  int rc = check_segs(seg32, nseg32, f32_numel, "16-bit", &s32);
-  if (rc) return rc;
-  rc = check_segs(seg64, nseg64, i64_numel, "int64", &s64);
-  if (rc) return rc;
-  fa_plan* p = new fa_plan();
-  p->elem = elem;
-  p->out_elem = out_elem;
-  p->info.f32_numel = f32_numel;
-  p->info.i64_numel = i64_numel;
-  p->info.tile_elems = tile_elems;
-  p->vec_u = tile_elems / fa_h16::kTile;
-  p->flags = flags | FA_PLAN_TUNE_NO_BALANCE;  // the plain table is the one launched
-  // the broadcast copies the bucket's bytes flat, as numel / 2 floats (a
-  // mixed plan's narrows element by element: any f32_numel)
-  p->flat_bcast = (flags & FA_PLAN_GAPS_ARE_PADDING) &&
-                  (f32_numel % 2 == 0 || out_elem == FA_ELEM_F32) &&
-                  covers_with_padding(s32, f32_numel, 128) &&
-                  covers_with_padding(s64, i64_numel, 1);
-  std::vector<Tile> tiles;
-  rc = build_tiles(s32, s64, tile_elems, flags, &tiles, &p->info, fa_h16::kVec);
-  if (rc) {
-    delete p;
-    return rc;
-  }
-  set_kinds(p, tiles);
-  hipError_t e = hipGetDevice(&p->device);
-  if (e == hipSuccess) e = upload_tables(p, tiles, {});
-  if (e != hipSuccess) {
-    (void)fa_plan_destroy(p);
-    return set_err(FA_E_HIP, "fa_plan_create_elem: %s", hipGetErrorString(e));
-  }
-  *out = p;
-  return FA_OK;
+int fa_plan_create(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
+                   int nseg64, int64_t i64_numel, int tile_elems, unsigned flags,
+                   fa_plan** out) {
+  return plan_create("fa_plan_create", " (removed tuning flags?)", seg32, nseg32, f32_numel, seg64,
+                     nseg64, i64_numel, tile_elems, flags, FA_ELEM_F32, FA_ELEM_F32, out);
 }
 
 int fa_plan_create_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
@@ -1511,21 +1144,10 @@ int fa_plan_create_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel, cons
   if (elem == FA_ELEM_F32)
     return fa_plan_create(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
                           out);
-  if (!out) return set_err(FA_E_INVAL, "fa_plan_create_elem: out is NULL");
-  *out = nullptr;
-  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
-    return set_err(FA_E_INVAL, "fa_plan_create_elem: unknown flag bits 0x%x",
-                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
-  if (f32_numel < 0 || i64_numel < 0) return set_err(FA_E_INVAL, "negative bucket size");
-  const int rc = check_elem(elem, &tile_elems, "fa_plan_create_elem");
-  if (rc) return rc;
-  return plan_create_h16(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
-                         elem, elem, out);
+  return plan_create("fa_plan_create_elem", "", seg32, nseg32, f32_numel, seg64, nseg64, i64_numel,
+                     tile_elems, flags, elem, elem, out);
 }
 
-// A mixed plan (elem 16-bit, out_elem FA_ELEM_F32): the 16-bit plan's table,
-// reduced by the wide-store instances of the 16-bit kernels into an fp32
-// bucket at the same element offsets, broadcast by the narrowing kernel.
 int fa_plan_create_elem_out(const fa_seg* seg32, int nseg32, int64_t f32_numel,
                             const fa_seg* seg64, int nseg64, int64_t i64_numel, int tile_elems,
                             unsigned flags, int elem, int out_elem, fa_plan** out) {
@@ -1538,14 +1160,8 @@ int fa_plan_create_elem_out(const fa_seg* seg32, int nseg32, int64_t f32_numel,
     return set_err(FA_E_INVAL, "fa_plan_create_elem_out: out_elem must equal elem, or be "
                                "FA_ELEM_F32 over FA_ELEM_F16 / FA_ELEM_BF16 clients (got elem %d, "
                                "out_elem %d)", elem, out_elem);
-  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
-    return set_err(FA_E_INVAL, "fa_plan_create_elem_out: unknown flag bits 0x%x",
-                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
-  if (f32_numel < 0 || i64_numel < 0) return set_err(FA_E_INVAL, "negative bucket size");
-  const int rc = check_elem(elem, &tile_elems, "fa_plan_create_elem_out");
-  if (rc) return rc;
-  return plan_create_h16(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
-                         elem, out_elem, out);
+  return plan_create("fa_plan_create_elem_out", "", seg32, nseg32, f32_numel, seg64, nseg64,
+                     i64_numel, tile_elems, flags, elem, out_elem, out);
 }
 
 int fa_plan_elem(const fa_plan* plan) {
@@ -1556,108 +1172,6 @@ int fa_plan_elem(const fa_plan* plan) {
 int fa_plan_out_elem(const fa_plan* plan) {
   if (!plan) return set_err(FA_E_INVAL, "fa_plan_out_elem: plan is NULL");
   return plan->out_elem;
-}
-
-int fa_plan_create(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
-                   int nseg64, int64_t i64_numel, int tile_elems, unsigned flags,
-                   fa_plan** out) {
-  if (!out) return set_err(FA_E_INVAL, "fa_plan_create: out is NULL");
-  *out = nullptr;
-  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
-    return set_err(FA_E_INVAL, "fa_plan_create: unknown flag bits 0x%x (removed tuning flags?)",
-                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
-  if (f32_numel < 0 || i64_numel < 0) return set_err(FA_E_INVAL, "negative bucket size");
-  const bool autosel = tile_elems == 0;
-  if (tile_elems == 0) tile_elems = 4 * kBlock * kDefaultU;
-  if (tile_elems != 4 * kBlock && tile_elems != 8 * kBlock && tile_elems != 16 * kBlock)
-    return set_err(FA_E_INVAL, "tile_elems must be 1024, 2048 or 4096 (got %d)", tile_elems);
-  std::vector<fa_seg> s32, s64;
-  int rc = check_segs(seg32, nseg32, f32_numel, "fp32", &s32);
-  if (rc) return rc;
-  rc = check_segs(seg64, nseg64, i64_numel, "int64", &s64);
-  if (rc) return rc;
-  fa_plan* p = new fa_plan();
-  p->info.f32_numel = f32_numel;
-  p->info.i64_numel = i64_numel;
-  p->info.tile_elems = tile_elems;
-  p->vec_u = tile_elems / (4 * kBlock);
-  p->flags = flags;
-  p->flat_bcast = flat_bcast_ok(flags, s32, f32_numel, s64, i64_numel);
-  std::vector<Tile> tiles, alt;
-  rc = build_tiles(s32, s64, tile_elems, flags, &tiles, &p->info);
-  if (rc) {
-    delete p;
-    return rc;
-  }
-  set_kinds(p, tiles);
-  if (autosel) {
-    fa_plan_info ia{};
-    rc = build_tiles(s32, s64, 4 * kBlock, flags, &alt, &ia);
-    if (rc) {
-      delete p;
-      return rc;
-    }
-    p->ntiles_alt = (int)alt.size();
-    p->nscalar_alt = ia.ntiles_tail;
-  }
-  hipError_t e = hipGetDevice(&p->device);
-  if (e == hipSuccess) e = upload_tables(p, tiles, alt);
-  if (e != hipSuccess) {
-    (void)fa_plan_destroy(p);  // frees whatever was uploaded
-    return set_err(FA_E_HIP, "fa_plan_create: %s", hipGetErrorString(e));
-  }
-  *out = p;
-  return FA_OK;
-}
-
-int fa_torch_gpu_config(int n, int64_t m, int* stride) {
-  if (n < 2 || m < 1) return 0;
-  auto last_pow2 = [](int64_t v) {
-    int64_t p = 1;
-    while (p * 2 <= v) p *= 2;
-    return p;
-  };
-  auto div_up = [](int64_t a, int64_t b) { return (a + b - 1) / b; };
-  int64_t S;
-  if (m == 1) {
-    // a 0-dim key stacked to [N]: lanes over the N values; from N >= 128 on
-    // torch vectorises the input (tgpu_inner_vec), and N <= FA_MAX_CLIENTS
-    // keeps values per thread below the cross-block threshold (N / 512 <
-    // 256).  `stride` is the block width.
-    S = n < 128 ? last_pow2(n) : std::min<int64_t>(last_pow2(n / 4), 512);
-  } else {
-    // setReduceConfig, "vectorize along output" ([N, M] reduced over dim 0,
-    // iter.ndim() == 2), set_block_dimension with MAX_NUM_THREADS 512
-    const int64_t ovs = m % 4 == 0 ? 4 : (m % 2 == 0 ? 2 : 1);
-    const int64_t mnt = 512 / ovs, dim0 = m / ovs;
-    const int64_t d0 = dim0 < mnt ? last_pow2(dim0) : mnt;
-    const int64_t d1 = n < mnt ? last_pow2(n) : mnt;
-    const int64_t bw0 = std::min<int64_t>(d0, 64);
-    const int64_t bh = std::min<int64_t>(d1, mnt / bw0);
-    const int64_t bw = std::min<int64_t>(d0, mnt / bh);
-    const bool split = n >= std::min<int64_t>(bh * 16, 256);
-    S = split ? bh : 1;
-    if (S > 16) return 0;  // kernel limit (tgpu_kernel<LS>, LS <= 4)
-    const int64_t vpt = div_up(n, S);
-    if (split && vpt >= 256) {
-      // the cross-block ("global") split: only when the output grid is
-      // small against the target grid (kTorchNumCU CUs; max threads per CU
-      // 256 for a 2-D iterator, the device's own for a single block —
-      // ROCm's `uses_a_single_block` reads grid.x == 1)
-      const int64_t grid = div_up(dim0, bw);
-      const int64_t tpm = grid == 1 ? kTorchMaxThreadsPerCU : 256;
-      const int64_t target = kTorchNumCU * (tpm / (bw * bh));
-      if (grid <= target) {
-        int64_t c = std::max(std::min(div_up(target, grid), div_up(vpt, 16)), div_up(vpt, 256));
-        if (c > kTorchNumCU) c = kTorchNumCU;
-        else if (c > div_up(kTorchNumCU, 2)) c = div_up(kTorchNumCU, 2);
-        else if (c < 16) c = 1;
-        if (c > 1) return 0;  // global_reduce: not restated
-      }
-    }
-  }
-  if (stride) *stride = (int)S;
-  return 1;
 }
 
 namespace {
@@ -1711,75 +1225,13 @@ size_t tgpu_s2_lds(int dev) {
                         : 0;
 }
 
-// Rows per load batch of the S = 1 tiles for a plan cut for n clients: 8
-// below 16 clients (as the default reduce's 8-client kernel; the 8-row form
-// holds 102 VGPRs against 164, five workgroups per CU against three):
-// measured r04 (tools/tgpu_speed.py, profiles/r04_tgpu_batch.jsonl) cfg3
-// N = 5 40.8 vs 45.8 us, but cfg2 N = 20 146.7 vs 140.9, cfg5 N = 24 173.9
-// vs 167.3.
-// r06: from 10 clients the 16-row form (three workgroups per CU) since the
-// client loop: same process (profiles/r06_ab_lib_tgpu_batch.jsonl) N = 10 / 12
-// -1.7 / -2.5 %, N = 2 / 5 / sf32 (N = 3) +1.3 / +3.8 / +1.6 %.
-#ifndef FA_TGPU_B16_MIN
-#define FA_TGPU_B16_MIN 10
-#endif
-int tgpu_batch_for(int n) { return n < FA_TGPU_B16_MIN ? 8 : 16; }
-
-// The tail round of launch group gi (the S = 1 group, r04; the default
-// plan's split_tail, §4.3 of DESIGN.md):
-// its scalar and inner tiles first; and when its T tiles spill
-// 0 < r <= 0.44 slots past k - 1 full rounds, the last slots - r wide tiles
-// are halved (64-element lines), so the table fills exactly k rounds with a
-// last round of half tiles instead of r tiles running alone.  cfg2 at N = 20: ~5,400 tiles on
-// 768 slots = 7.03 rounds.  Per-column arithmetic: the bits never change.
-void tgpu_split_tail(std::vector<Tile>* t, std::vector<float>* fac, int lo[6], int gi, int slots) {
-  const int64_t T = lo[gi + 1] - lo[gi];
-  const int64_t k = slots > 0 ? (T + slots - 1) / slots : 0;
-  const int64_t r = T - (k - 1) * slots;
-  // m: the wide tiles to halve (0: none; the group is still reordered so
-  // its scalar and inner tiles — the int64 keys' one-wave latency chains —
-  // run in the first round, as the default plan places its scalar tiles)
-  const int64_t m = (k > 1 && r > 0 && r * 100 <= kTailMaxPct * (int64_t)slots) ? slots - r : 0;
-  std::vector<Tile> nw, wd;
-  std::vector<float> fnw, fwd;
-  for (int64_t i = lo[gi]; i < lo[gi + 1]; ++i) {
-    const bool w = ((*t)[i].kind & 0xFF) == K_F32_TGPU_W;
-    (w ? wd : nw).push_back((*t)[i]);
-    (w ? fwd : fnw).push_back((*fac)[i]);
-  }
-  std::vector<Tile> g(t->begin(), t->begin() + lo[gi]);
-  std::vector<float> f(fac->begin(), fac->begin() + lo[gi]);
-  g.insert(g.end(), nw.begin(), nw.end());
-  f.insert(f.end(), fnw.begin(), fnw.end());
-  const size_t first = (int64_t)wd.size() < m ? wd.size() : wd.size() - (size_t)m;
-  for (size_t j = 0; j < wd.size(); ++j) {
-    const Tile& x = wd[j];
-    const int64_t h = ((int64_t)x.count / 2) & ~(int64_t)63;
-    if (j < first || h < 64) {
-      g.push_back(x);
-      f.push_back(fwd[j]);
-      continue;
-    }
-    g.push_back(Tile{x.start, (int32_t)h, x.kind});
-    g.push_back(Tile{x.start + h, (int32_t)(x.count - h), x.kind});
-    f.push_back(fwd[j]);
-    f.push_back(fwd[j]);
-  }
-  const int add = (int)((int64_t)g.size() - lo[gi] - T);
-  g.insert(g.end(), t->begin() + lo[gi + 1], t->end());
-  f.insert(f.end(), fac->begin() + lo[gi + 1], fac->end());
-  t->swap(g);
-  fac->swap(f);
-  for (int i = gi + 1; i < 6; ++i) lo[i] += add;
-}
 }  // namespace
 
 int fa_plan_create_order(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
                          int nseg64, int64_t i64_numel, int n, int order, unsigned flags,
                          fa_plan** out) {
-  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
-    return set_err(FA_E_INVAL, "fa_plan_create_order: unknown flag bits 0x%x",
-                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
+  int rc = fa_host::check_flags("fa_plan_create_order", flags);
+  if (rc) return rc;
   if (order == FA_ORDER_TORCH_CPU)
     return fa_plan_create(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags, out);
   if (!out) return set_err(FA_E_INVAL, "fa_plan_create_order: out is NULL");
@@ -1788,233 +1240,45 @@ int fa_plan_create_order(const fa_seg* seg32, int nseg32, int64_t f32_numel, con
     return set_err(FA_E_INVAL, "fa_plan_create_order: order %d", order);
   if (n < 2 || n > FA_MAX_CLIENTS)
     return set_err(FA_E_RANGE, "fa_plan_create_order: n=%d outside 2..%d", n, FA_MAX_CLIENTS);
-  std::vector<fa_seg> s32, s64;
-  int rc = check_segs(seg32, nseg32, f32_numel, "fp32", &s32);
+  fa_host::Layout l;
+  rc = fa_host::parse_layout("fa_plan_create_order", "", 0, seg32, nseg32, f32_numel, seg64,
+                             nseg64, i64_numel, 4 * kBlock, flags, FA_ELEM_F32, &l);
   if (rc) return rc;
-  rc = check_segs(seg64, nseg64, i64_numel, "int64", &s64);
+  // the planner's one device input: the S = 1 launch's resident workgroups
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  const int slots = e == hipSuccess && !(flags & FA_PLAN_TUNE_NO_BALANCE)
+                        ? tgpu_slots(dev, fa_host::tgpu_batch_for(n))
+                        : 0;
+  fa_host::TgpuTables t;
+  rc = fa_host::plan_tgpu(l.s32, l.s64, n, flags, slots, &t);
   if (rc) return rc;
-  std::vector<Tile> t;
-  std::vector<float> fac;
-  std::vector<int> order_groups_tmp;
-  // Wide S = 1 runs.  With S = 1 every M > 1 tensor has the same per-element
-  // order (row p into accumulator p % 4, then ((a0 + a1) + a2) + a3), so the
-  // 4-aligned bodies of adjacent such tensors with the same factor (bit for
-  // bit) share one run cut into 2048-element tiles across key boundaries, as
-  // the default plan's vector runs are: no partial tile per key (cfg2: 5432
-  // -> ~5381 tiles).  Gaps join a run only when declared padding.
-  // r06: runs of every row split S (the order depends on (N, S) only, as for
-  // S = 1; S <= 2 in 2048-element W tiles, S >= 4 in 1024-element V tiles),
-  // and adjacent one-element keys of one kind packed a wave each into one
-  // tile: wrn16_8 C10 at N = 32 / 48 / 64 then fills 7 rounds of the S = 2
-  // launch's 768 slots (5,372 / 5,372 / 5,370 tiles) where per-key tiles
-  // spilled past them (5,417 / 5,417 / 5,432)
-  int64_t run_s = -1, run_e = -1;
-  int run_ls = 0;
-  float run_f = 0.f;
-  auto flush = [&]() {
-    if (run_s < 0) return;
-    const int64_t te = run_ls <= 1 ? 8 * kBlock : 4 * kBlock;
-    const int kind = (run_ls <= 1 ? K_F32_TGPU_W : K_F32_TGPU_V) | (run_ls << 8);
-    for (int64_t c = run_s; c < run_e; c += te) {
-      t.push_back(Tile{c, (int32_t)std::min<int64_t>(te, run_e - c), kind});
-      fac.push_back(run_f);
-    }
-    run_s = run_e = -1;
-  };
-  for (int pass = 0; pass < 2; ++pass) {
-    flush();
-    for (const fa_seg& g : pass ? s64 : s32) {
-      if (g.numel == 0) continue;
-      int S = 1;
-      if (!fa_torch_gpu_config(n, g.numel, &S))
-        return set_err(FA_E_RANGE,
-                       "torch-GPU order: N=%d over a %lld-element tensor is outside the "
-                       "restated configurations (cross-block split)", n, (long long)g.numel);
-      int ls = 0;
-      while ((1 << ls) < S) ++ls;
-      // torch's factor: float(num_outputs) / numel, in float
-      const float f = (float)g.numel / (float)((int64_t)n * g.numel);
-      if (g.numel == 1) {
-        flush();
-        const int vec = n >= 128 ? 1 << 16 : 0;  // input-vectorised (tgpu_inner_vec)
-        const int kind = (pass ? K_I64_TGPU_IN : K_F32_TGPU_IN) | (ls << 8) | vec;
-        if (!t.empty() && t.back().kind == kind && fac.back() == f &&
-            t.back().start + t.back().count == g.offset && t.back().count < kBlock / 64) {
-          t.back().count++;   // one wave per element (tgpu_kernel's inner form)
-          continue;
-        }
-        t.push_back(Tile{g.offset, 1, kind});
-        fac.push_back(f);
-        continue;
-      }
-      auto scalar = [&](int64_t lo, int64_t hi) {
-        for (int64_t c = lo; c < hi; c += kBlock) {
-          t.push_back(Tile{g.offset + c, (int32_t)std::min<int64_t>(kBlock, hi - c),
-                           (pass ? K_I64_TGPU : K_F32_TGPU) | (ls << 8)});
-          fac.push_back(f);
-        }
-      };
-      if (pass) {
-        scalar(0, g.numel);
-        continue;
-      }
-      // fp32: the 16-B aligned body in 4-element-per-lane tiles, the <= 3
-      // element head and tail one element per lane (same order, same factor)
-      const int64_t head = std::min<int64_t>((4 - g.offset % 4) % 4, g.numel);
-      const int64_t body = (g.numel - head) / 4 * 4;
-      // S = 1: 2048-element tiles, the default reduce's load shape (r02:
-      // 151.9 us on cfg2 with the 1024-element form); S = 2 too since r05
-      // (tgpu_wide_loop); a key whose body is not 16-B aligned keeps its own
-      // tiles
-      const bool wide = S <= 2;
-      if (head == 0 && body > 0) {
-        const bool extend = run_s >= 0 && run_f == f && run_ls == ls &&
-                            (run_e == g.offset ||
-                             ((flags & FA_PLAN_GAPS_ARE_PADDING) && run_e <= g.offset));
-        if (!extend) flush();
-        if (run_s < 0) {
-          run_s = g.offset;
-          run_f = f;
-          run_ls = ls;
-        }
-        run_e = g.offset + body;
-        if (body < g.numel) {
-          flush();  // the tail breaks the run
-          scalar(body, g.numel);
-        }
-        continue;
-      }
-      flush();
-      scalar(0, head);
-      const int64_t te = wide ? 8 * kBlock : 4 * kBlock;
-      for (int64_t c = head; c < head + body; c += te) {
-        t.push_back(Tile{g.offset + c, (int32_t)std::min<int64_t>(te, head + body - c),
-                         (wide ? K_F32_TGPU_W : K_F32_TGPU_V) | (ls << 8)});
-        fac.push_back(f);
-      }
-      scalar(head + body, g.numel);
-    }
-  }
-  flush();
-  rc = check_disjoint(t, "torch-GPU order planner");
-  if (rc) return rc;
-  // group the tiles by row split (inner tiles with S = 1): one launch each.
-  // r05: when the S = 2 group holds the most tiles, the S = 1, S = 4 and
-  // inner tiles ride in its launch, first (tgpu_kernel<1>; the small groups'
-  // own launches cost 10-13 us of latency each at N = 32..127).  With the
-  // S = 2 tiles wide, same process against the build before
-  // (profiles/r05_ab_lib_tgpu_s2.jsonl): N = 32 / 48 / 64 / 100 / 127
-  // -10.0 / -10.2 / -12.2 / -10.6 / -7.8 %, C100 N = 64 / 128 -11.6 / -6.0 %
-  // (0.83-0.85 of 8 TB/s); S = 1 riders only: 1-3 points less
-  {
-    std::vector<int> grp(t.size());
-    int cnt[5] = {0, 0, 0, 0, 0};
-    for (size_t i = 0; i < t.size(); ++i) {
-      const int b = t[i].kind & 0xFF;
-      grp[i] = (b == K_F32_TGPU_IN || b == K_I64_TGPU_IN) ? 0 : (t[i].kind >> 8) & 0xFF;
-      cnt[grp[i]]++;
-    }
-    const bool ride = cnt[1] > 0 && cnt[1] >= cnt[0] && cnt[1] >= cnt[2];
-    // sort key: launch group, riders before the group's own tiles
-    std::vector<int> key(t.size());
-    for (size_t i = 0; i < t.size(); ++i) {
-      const bool rider = ride && (grp[i] == 0 || grp[i] == 2);
-      // tgpu_kernel<1> reduces every vector (V) rider with the S = 4 path: S = 1
-      // keys never make V tiles (wide = S <= 2 above); refuse a table that
-      // would, rather than reduce it in the wrong order
-      if (rider && (t[i].kind & 0xFF) == K_F32_TGPU_V && ((t[i].kind >> 8) & 0xFF) != 2)
-        return set_err(FA_E_INVAL, "torch-GPU order planner: a vector rider of row split %d",
-                       1 << ((t[i].kind >> 8) & 0xFF));
-      if (rider) grp[i] = 1;
-      key[i] = 2 * grp[i] + (rider ? 0 : 1);
-    }
-    std::vector<size_t> ord(t.size());
-    for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
-    std::stable_sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return key[x] < key[y]; });
-    std::vector<Tile> t2;
-    std::vector<float> f2;
-    for (size_t i : ord) {
-      t2.push_back(t[i]);
-      f2.push_back(fac[i]);
-    }
-    t.swap(t2);
-    fac.swap(f2);
-    int lo[6] = {0, 0, 0, 0, 0, 0};
-    for (size_t i = 0; i < ord.size(); ++i) lo[grp[ord[i]] + 1]++;
-    for (int g = 0; g < 5; ++g) lo[g + 1] += lo[g];
-    if (!(flags & FA_PLAN_TUNE_NO_BALANCE)) {
-      int dev = 0;
-      if (hipGetDevice(&dev) == hipSuccess) {
-        tgpu_split_tail(&t, &fac, lo, 0, tgpu_slots(dev, tgpu_batch_for(n)));
-        // r06: the same halving on the S = 2 launch measured neutral at
-        // N = 32 / 64 / 100, -2.7 % at N = 48, +0.5 % on C100 N = 128
-        // (profiles/r06_ab_lib_tgpu_runs.jsonl, variant "nobal"): not applied
-      }
-    }
-    order_groups_tmp.assign(lo, lo + 6);
-  }
-  fa_plan* p = new fa_plan();
-  for (int g = 0; g < 6; ++g) p->tg_lo[g] = order_groups_tmp[g];
-  p->info.f32_numel = f32_numel;
-  p->info.i64_numel = i64_numel;
-  p->info.tile_elems = 4 * kBlock;
-  p->info.ntiles = (int32_t)t.size();
-  p->info.ntiles_tail = (int32_t)t.size();
+  PlanPtr p(new fa_plan());
+  for (int g = 0; g < 6; ++g) p->tg_lo[g] = t.lo[g];
+  p->info = l.info;
+  p->info.ntiles = (int32_t)t.tiles.size();
+  p->info.ntiles_tail = (int32_t)t.tiles.size();
   p->flags = flags;
-  p->flat_bcast = flat_bcast_ok(flags, s32, f32_numel, s64, i64_numel);
+  p->flat_bcast = fa_host::flat_bcast_ok(flags, l, FA_ELEM_F32, FA_ELEM_F32);
   p->order = FA_ORDER_TORCH_GPU;
   p->order_n = n;
-  p->tgpu_batch = tgpu_batch_for(n);
-  for (const Tile& x : t) (kind_is64(x.kind) ? p->has64 : p->has32) = true;
-  hipError_t e = hipGetDevice(&p->device);
-  if (e == hipSuccess) p->tgpu_s2_lds = tgpu_s2_lds(p->device);
-  if (e == hipSuccess && !t.empty()) {
-    e = hipMalloc(&p->d_tiles, t.size() * sizeof(Tile));
-    if (e == hipSuccess)
-      e = hipMemcpy(p->d_tiles, t.data(), t.size() * sizeof(Tile), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&p->d_fac, fac.size() * sizeof(float));
-    if (e == hipSuccess)
-      e = hipMemcpy(p->d_fac, fac.data(), fac.size() * sizeof(float), hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    if (p->d_tiles) (void)hipFree(p->d_tiles);
-    if (p->d_fac) (void)hipFree(p->d_fac);
-    delete p;
+  p->tgpu_batch = fa_host::tgpu_batch_for(n);
+  set_kinds(p.get(), t.tiles);
+  p->device = dev;
+  if (e == hipSuccess) p->tgpu_s2_lds = tgpu_s2_lds(dev);
+  if (e == hipSuccess) e = upload(&p->d_tiles, t.tiles);
+  if (e == hipSuccess) e = upload(&p->d_fac, t.fac);
+  if (e != hipSuccess)
     return set_err(FA_E_HIP, "fa_plan_create_order: %s", hipGetErrorString(e));
-  }
-  *out = p;
+  *out = p.release();
   return FA_OK;
 }
 
 int fa_plan_build_host(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
                        int nseg64, int64_t i64_numel, int tile_elems, unsigned flags,
                        fa_tile_desc* tiles, int cap, fa_plan_info* info) {
-  if (!info) return set_err(FA_E_INVAL, "fa_plan_build_host: info is NULL");
-  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
-    return set_err(FA_E_INVAL, "fa_plan_build_host: unknown flag bits 0x%x",
-                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
-  if (tile_elems == 0) tile_elems = 4 * kBlock * kDefaultU;
-  if (tile_elems != 4 * kBlock && tile_elems != 8 * kBlock && tile_elems != 16 * kBlock)
-    return set_err(FA_E_INVAL, "tile_elems must be 1024, 2048 or 4096 (got %d)", tile_elems);
-  std::vector<fa_seg> s32, s64;
-  int rc = check_segs(seg32, nseg32, f32_numel, "fp32", &s32);
-  if (rc) return rc;
-  rc = check_segs(seg64, nseg64, i64_numel, "int64", &s64);
-  if (rc) return rc;
-  fa_plan_info in{};
-  in.f32_numel = f32_numel;
-  in.i64_numel = i64_numel;
-  in.tile_elems = tile_elems;
-  std::vector<Tile> t;
-  rc = build_tiles(s32, s64, tile_elems, flags, &t, &in);
-  if (rc) return rc;
-  *info = in;
-  if (tiles) {
-    if (cap < (int)t.size())
-      return set_err(FA_E_RANGE, "fa_plan_build_host: %d tiles, capacity %d", (int)t.size(), cap);
-    for (size_t i = 0; i < t.size(); ++i) tiles[i] = fa_tile_desc{t[i].start, t[i].count, t[i].kind};
-  }
-  return FA_OK;
+  return plan_build_host("fa_plan_build_host", seg32, nseg32, f32_numel, seg64, nseg64, i64_numel,
+                         tile_elems, flags, FA_ELEM_F32, tiles, cap, info);
 }
 
 int fa_plan_build_host_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel,
@@ -2024,32 +1288,8 @@ int fa_plan_build_host_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel,
   if (elem == FA_ELEM_F32)
     return fa_plan_build_host(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems,
                               flags, tiles, cap, info);
-  if (!info) return set_err(FA_E_INVAL, "fa_plan_build_host_elem: info is NULL");
-  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
-    return set_err(FA_E_INVAL, "fa_plan_build_host_elem: unknown flag bits 0x%x",
-                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
-  int rc = check_elem(elem, &tile_elems, "fa_plan_build_host_elem");
-  if (rc) return rc;
-  std::vector<fa_seg> s32, s64;
-  rc = check_segs(seg32, nseg32, f32_numel, "16-bit", &s32);
-  if (rc) return rc;
-  rc = check_segs(seg64, nseg64, i64_numel, "int64", &s64);
-  if (rc) return rc;
-  fa_plan_info in{};
-  in.f32_numel = f32_numel;
-  in.i64_numel = i64_numel;
-  in.tile_elems = tile_elems;
-  std::vector<Tile> t;
-  rc = build_tiles(s32, s64, tile_elems, flags, &t, &in, fa_h16::kVec);
-  if (rc) return rc;
-  *info = in;
-  if (tiles) {
-    if (cap < (int)t.size())
-      return set_err(FA_E_RANGE, "fa_plan_build_host_elem: %d tiles, capacity %d", (int)t.size(),
-                     cap);
-    for (size_t i = 0; i < t.size(); ++i) tiles[i] = fa_tile_desc{t[i].start, t[i].count, t[i].kind};
-  }
-  return FA_OK;
+  return plan_build_host("fa_plan_build_host_elem", seg32, nseg32, f32_numel, seg64, nseg64,
+                         i64_numel, tile_elems, flags, elem, tiles, cap, info);
 }
 
 int fa_plan_create_from_tiles(const fa_tile_desc* tiles, int ntiles, int64_t f32_numel,
@@ -2057,15 +1297,13 @@ int fa_plan_create_from_tiles(const fa_tile_desc* tiles, int ntiles, int64_t f32
                               fa_plan** out) {
   if (!out) return set_err(FA_E_INVAL, "fa_plan_create_from_tiles: out is NULL");
   *out = nullptr;
-  if (flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN)
-    return set_err(FA_E_INVAL, "fa_plan_create_from_tiles: unknown flag bits 0x%x",
-                   flags & ~(unsigned)FA_PLAN_FLAGS_KNOWN);
+  int rc = fa_host::check_flags("fa_plan_create_from_tiles", flags);
+  if (rc) return rc;
   if (ntiles < 0 || (ntiles > 0 && !tiles))
     return set_err(FA_E_INVAL, "fa_plan_create_from_tiles: bad tile array");
   if (tile_elems == 0) tile_elems = 4 * kBlock * kDefaultU;
   if (tile_elems != 4 * kBlock && tile_elems != 8 * kBlock && tile_elems != 16 * kBlock)
     return set_err(FA_E_INVAL, "tile_elems must be 1024, 2048 or 4096 (got %d)", tile_elems);
-  std::vector<Tile> t(ntiles);
   fa_plan_info in{};
   in.f32_numel = f32_numel;
   in.i64_numel = i64_numel;
@@ -2091,28 +1329,23 @@ int fa_plan_create_from_tiles(const fa_tile_desc* tiles, int ntiles, int64_t f32
       if (!is64) in.tail_elems += d.count;
     }
   }
-  t.clear();
-  t.insert(t.end(), sc.begin(), sc.end());
+  std::vector<Tile> t(sc);
   t.insert(t.end(), vec.begin(), vec.end());
-  const int rc = check_disjoint(t, "fa_plan_create_from_tiles");
+  rc = fa_host::check_disjoint(t, "fa_plan_create_from_tiles");
   if (rc) return rc;
   in.ntiles = (int32_t)t.size();
   in.ntiles_cascade = (int32_t)vec.size();
   in.ntiles_tail = (int32_t)sc.size();
-  fa_plan* p = new fa_plan();
+  PlanPtr p(new fa_plan());
   p->info = in;
   p->vec_u = tile_elems / (4 * kBlock);
   p->flags = flags | FA_PLAN_TUNE_NO_BALANCE;  // the caller's tiles are the ones launched
-  set_kinds(p, t);
+  set_kinds(p.get(), t);
   hipError_t e = hipGetDevice(&p->device);
-  if (e == hipSuccess) e = upload_tables(p, t, {});
-  if (e != hipSuccess) {
-    if (p->d_tiles) (void)hipFree(p->d_tiles);
-    if (p->d_sidx) (void)hipFree(p->d_sidx);
-    delete p;
+  if (e == hipSuccess) e = upload_tables(p.get(), t, {});
+  if (e != hipSuccess)
     return set_err(FA_E_HIP, "fa_plan_create_from_tiles: %s", hipGetErrorString(e));
-  }
-  *out = p;
+  *out = p.release();
   return FA_OK;
 }
 
@@ -2122,8 +1355,7 @@ int fa_plan_destroy(fa_plan* plan) {
   if (plan->d_tiles) HIP_TRY(hipFree(plan->d_tiles));
   if (plan->d_tiles_alt) HIP_TRY(hipFree(plan->d_tiles_alt));
   if (plan->d_sidx) HIP_TRY(hipFree(plan->d_sidx));
-  for (const fa_plan::BalTable& b : plan->bal)
-    if (b.d) HIP_TRY(hipFree(b.d));
+  for (Tile* d : plan->d_bal) HIP_TRY(hipFree(d));
   delete plan;
   return FA_OK;
 }
@@ -2183,94 +1415,6 @@ hipError_t launch_bcast(const fa_plan* plan, ReduceArgs& a, int n, int ntiles, h
 }
 }  // namespace
 
-}  // extern "C"
-namespace {
-// The table, packed-tile count, scalar index and tile width a plain reduce
-// call runs with (fa_reduce; fa_plan_launch_shape reports it).
-struct Launch {
-  const Tile* tiles;
-  int nt, ns;
-  const int64_t* sidx;
-  int vec_u;
-  int slots;  // resident workgroups of its kernel (0: unknown / tuning grid)
-  int batch;  // clients per load batch of its kernel
-};
-// The next client's loads before the current client's adds
-// (reduce_impl.h pipe2_clients) where it measured faster
-// (profiles/r05_exp_pipe2_*.jsonl, r05_ab_lib_pipe2_*.jsonl): calls of 2..7
-// or 17..63 clients (inline pointers), mean or weighted, on the full
-// 2048-float tiles of launches of three or more rounds of resident
-// workgroups (partial tiles — tensor ends, the halved tail of a table re-cut
-// for the round count — keep the batch form).  Not the 1024-float table, not
-// 8..16 clients (r05: on the 8-client kernels), not the short launches
-// (resnet110sl N = 25 at two rounds: +0.9 %; sf32 N = 3 at 2.5: +0.8 %).
-// r06: 12..16 clients on the 16-client kernels (pick_batch, FA_B16_MIN);
-// unweighted calls of 64..128 clients too, now on the 2048-float table
-// (select_launch): same process against the 1024-float table's batch form
-// (profiles/r06_ab_lib_n64.jsonl, two boxes) C10 N = 64 / 100 / 128 -3.5 /
-// -3.1 / -3.2 % and -3.1 / -2.5 / -2.6 %, C100 N = 64 / 100 -3.0 / -2.5 % and
-// -0.3 / -2.2 %, bits equal; the 2048-float table in the batch form alone
-// -1.8 / -3.0 / -3.3 / -1.8 / -2.0 %.  Weighted calls from 64 keep the batch
-// form (r05: the loop +0.4 / +2.4 % at 80 / 128; r06 again: -0.7 / +0.3 /
-// +1.2 / +3.2 % at 64 / 80 / 100 / 128, profiles/r06_ab_lib_w64_loop.jsonl).
-int pipe_rule(const fa_plan* plan, const Launch& L, int n, bool weighted) {
-  (void)plan;
-  // r06: unweighted calls of 256 clients and more (the DEEP cascade) on the
-  // 2048-float table, the loop reading the device pointer table through
-  // scalar loads (PIPE = 2): same process against the 1024-float table's
-  // batch form (profiles/r06_ab_lib_tab_loop.jsonl) N = 256 / 300 -1.9 /
-  // -3.8 %; at 129..255 (not deep) +0.2 / +3.5 % at 150 / 200, so those keep
-  // the 1024-float table.  Bits equal.
-  if (n > kInline)
-    return (!weighted && n >= 256 && L.vec_u == 2 && L.batch == 16 && L.slots > 0 &&
-            L.nt >= 3 * L.slots)
-               ? 2
-               : 0;
-  if (n > kInline || L.vec_u != 2 || L.slots <= 0 || L.nt < 3 * L.slots) return 0;
-#ifndef FA_PIPE_MID_LO
-#define FA_PIPE_MID_LO FA_B16_MIN
-#endif
-  return (n >= 2 && n <= 7) || (n >= FA_PIPE_MID_LO && n <= 63) || (!weighted && n >= 64) ? 1
-                                                                                            : 0;
-}
-
-
-Launch select_launch(const fa_plan* plan, int n, bool weighted, unsigned flags) {
-  Launch L{plan->d_tiles, plan->nt_dev, plan->ns_dev, plan->d_sidx, plan->vec_u, 0, 0};
-  bool alt = false;
-  (void)flags;
-  // 1024-float tiles for unweighted calls of 129..255 clients (r02's
-  // tools/tune.py sweep took them from N = 64; r06: 64..128 and from 256 run
-  // faster on the 2048-float table with the client loop, see pipe_rule; the
-  // 2048-float table at N = 200 +3.7 % in the batch form, +3.5 % with the loop)
-  if (plan->d_tiles_alt && !weighted && n > kInline && n < 256) {
-    L.tiles = plan->d_tiles_alt;
-    L.nt = plan->nt_alt_dev;
-    L.ns = plan->ns_alt_dev;
-    L.sidx = plan->d_sidx ? plan->d_sidx + plan->sidx_alt_off : nullptr;
-    L.vec_u = 1;
-    alt = true;
-  }
-  // the batch: 8 where that runs the plain table in one round instead of two
-  L.batch = round_batch(plan->device, n, L.vec_u, weighted, plan->flags, L.nt);
-  L.slots = call_slots(plan->device, n, L.vec_u, weighted, plan->flags);
-  if (L.batch != pick_batch(n, L.vec_u, plan->flags)) {
-    L.slots = kernel_slots(plan->device, L.vec_u, L.batch, n >= 256, weighted);
-  } else if (!plan->bal.empty()) {
-    // the table cut for the slot count of the kernel this call runs
-    for (const fa_plan::BalTable& b : plan->bal)
-      if (b.slots == L.slots && b.u == L.vec_u && b.alt == alt && b.batch == L.batch) {
-        L.tiles = b.d;
-        L.nt = b.nt;
-        break;
-      }
-  }
-  return L;
-}
-}  // namespace
-
-extern "C" {
-
 int fa_plan_balance_host(const fa_tile_desc* vec, int nvec, int tile_elems, int nscalar,
                          int slots, fa_tile_desc* out, int cap) {
   if (nvec < 0 || (nvec > 0 && !vec) || nscalar < 0 || slots < 0 || cap < 0 ||
@@ -2285,7 +1429,7 @@ int fa_plan_balance_host(const fa_tile_desc* vec, int nvec, int tile_elems, int 
       return set_err(FA_E_INVAL, "fa_plan_balance_host: tile %d is not a vector tile", i);
     t.push_back(Tile{vec[i].start, vec[i].count, vec[i].kind});
   }
-  const std::vector<Tile> b = balance_vec(t, tile_elems, nscalar, slots);
+  const std::vector<Tile> b = fa_host::balance_vec(t, tile_elems, nscalar, slots);
   if ((int64_t)b.size() > (int64_t)cap)
     return set_err(FA_E_RANGE, "fa_plan_balance_host: %zu tiles > cap %d", b.size(), cap);
   for (size_t i = 0; i < b.size(); ++i) out[i] = fa_tile_desc{b[i].start, b[i].count, b[i].kind};
@@ -2301,15 +1445,15 @@ int fa_plan_launch_shape(const fa_plan* plan, int n, int weighted, int* ntiles, 
     return FA_OK;
   }
   if (plan->elem != FA_ELEM_F32) {  // one table, launched as it is
-    *ntiles = plan->nt_dev;
+    *ntiles = plan->nt;
     *slots = 0;
     return FA_OK;
   }
-  const Launch L = select_launch(plan, n, weighted != 0, 0);
+  const fa_host::Launch L = fa_host::select_launch(*plan, n, weighted != 0, kernel_slots);
   *ntiles = L.nt;
   *slots = L.slots ? L.slots
-                   : call_slots(plan->device, n, L.vec_u, weighted != 0,
-                                plan->flags & ~FA_PLAN_TUNE_NO_BALANCE);
+                   : fa_host::call_slots(plan->device, n, L.vec_u, weighted != 0,
+                                         plan->flags & ~FA_PLAN_TUNE_NO_BALANCE, kernel_slots);
   return FA_OK;
 }
 
@@ -2329,10 +1473,10 @@ int fa_plan_launch_form(const fa_plan* plan, int n, int weighted, int* tile_elem
     *pipe = 1;
     return FA_OK;
   }
-  const Launch L = select_launch(plan, n, weighted != 0, 0);
+  const fa_host::Launch L = fa_host::select_launch(*plan, n, weighted != 0, kernel_slots);
   *tile_elems = 4 * kBlock * L.vec_u;
   *batch = L.batch;
-  *pipe = pipe_rule(plan, L, n, weighted != 0);
+  *pipe = L.pipe;
   return FA_OK;
 }
 
@@ -2344,6 +1488,135 @@ int fa_reduce(const fa_plan* plan, const float* const* c32, const int64_t* const
   return fa_reduce_tab(plan, c32, c64, n, weights, nullptr, out32, out64, flags, stream);
 }
 
+namespace {
+// A call's client pointers and weights.  n <= kInline: copied into the
+// kernel arguments, no allocation and no HIP call.  More: a device table
+// [n fp32 ptrs][n int64 ptrs][n weights] — the caller's (ctable: written by
+// kernels, no memcpy), or a stream-ordered allocation that done() / the
+// scope's end frees on the stream.  c32 / c64 NULL: that bucket is not read.
+struct ClientTable {
+  hipStream_t st;
+  void* owned = nullptr;
+
+  hipError_t fill(ReduceArgs& a, const float* const* c32, const int64_t* const* c64, int n,
+                  const float* weights, void* ctable) {
+    if (n <= kInline) {
+      for (int i = 0; i < n; ++i) {
+        if (c32) a.c32[i] = c32[i];
+        if (c64) a.c64[i] = c64[i];
+        if (weights) a.w[i] = weights[i];
+      }
+      return hipSuccess;
+    }
+    std::vector<char> host((size_t)n * 20);
+    const void** h32 = (const void**)host.data();
+    const void** h64 = h32 + n;
+    float* hw = (float*)(h64 + n);
+    for (int i = 0; i < n; ++i) {
+      h32[i] = c32 ? (const void*)c32[i] : nullptr;
+      h64[i] = c64 ? (const void*)c64[i] : nullptr;
+      hw[i] = weights ? weights[i] : 0.f;
+    }
+    hipError_t e;
+    if (ctable) {
+      e = table_fill(ctable, host, st);
+    } else {
+      e = table_alloc(&owned, host.size(), st);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(owned, host.data(), host.size(), hipMemcpyHostToDevice, st);
+    }
+    const void** tab = (const void**)(ctable ? ctable : owned);
+    a.tab32 = (const float* const*)tab;
+    a.tab64 = (const int64_t* const*)(tab + n);
+    a.tabw = (const float*)(tab + 2 * n);
+    return e;
+  }
+  // the call's outcome: `e`, or the free's error when the launches went well
+  hipError_t done(hipError_t e) {
+    if (owned) {
+      const hipError_t e2 = hipFreeAsync(owned, st);
+      owned = nullptr;
+      if (e == hipSuccess) e = e2;
+    }
+    return e;
+  }
+  ~ClientTable() { (void)done(hipSuccess); }
+};
+
+// the broadcast alone (the reference's initial sync, train_fedavg.py:
+// 244-250, and :148-149 without the reduce): out32/out64 -> every client
+hipError_t run_bcast_only(const fa_plan* plan, ReduceArgs& a, int n, hipStream_t st) {
+  const int nt = plan->order == FA_ORDER_TORCH_GPU ? plan->info.ntiles : plan->nt;
+  a.ntiles = nt;
+  a.sidx = plan->d_sidx;
+  return launch_bcast(plan, a, n, nt, st);
+}
+
+// one launch per row-split group of the plan's table; the broadcast as its
+// own launch over the whole table, client groups per tile (as the default
+// order's split broadcast)
+hipError_t run_tgpu(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  for (int g = 0; g < 5 && e == hipSuccess; ++g) {
+    const int lo = plan->tg_lo[g], cnt = plan->tg_lo[g + 1] - lo;
+    if (cnt == 0) continue;
+    a.tiles = plan->d_tiles + lo;
+    a.tfac = plan->d_fac + lo;
+    a.ntiles = cnt;
+    switch (g) {
+      case 0:
+        // the client loop on full tiles at every N (r05,
+        // profiles/r05_ab_lib_tgpu_client_loop.jsonl)
+        if (plan->tgpu_batch == 8)
+          hipLaunchKernelGGL((tgpu_kernel<0, 8, 1>), dim3(cnt), dim3(kBlock), 0, st, a);
+        else
+          hipLaunchKernelGGL((tgpu_kernel<0, 16, 1>), dim3(cnt), dim3(kBlock), 0, st, a);
+        break;
+      case 1:
+        hipLaunchKernelGGL(tgpu_kernel<1>, dim3(cnt), dim3(kBlock), plan->tgpu_s2_lds, st, a);
+        break;
+      case 2: hipLaunchKernelGGL(tgpu_kernel<2>, dim3(cnt), dim3(kBlock), 0, st, a); break;
+      case 3: hipLaunchKernelGGL(tgpu_kernel<3>, dim3(cnt), dim3(kBlock), 0, st, a); break;
+      default: hipLaunchKernelGGL(tgpu_kernel<4>, dim3(cnt), dim3(kBlock), 0, st, a); break;
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && bcast && plan->tg_lo[5] > 0) {
+    a.tiles = plan->d_tiles;
+    a.ntiles = plan->tg_lo[5];
+    e = launch_bcast(plan, a, n, a.ntiles, st);
+  }
+  return e;
+}
+
+// the 16-bit kernels (fedagg_h16.hip) over the plan's one table, then the
+// broadcast's flat copy of the result bucket
+hipError_t run_h16(const fa_plan* plan, ReduceArgs& a, int n, bool weighted, bool bcast,
+                   hipStream_t st) {
+  a.nscalar = plan->ns;
+  a.sidx = plan->d_sidx;
+  a.ntiles = plan->nt;
+  hipError_t e = fa_h16::launch(a, plan->nt, plan->elem, plan->vec_u, weighted,
+                                plan->out_elem == FA_ELEM_F32, st);
+  if (e == hipSuccess && bcast) e = launch_bcast(plan, a, n, plan->nt, st);
+  return e;
+}
+
+// the table and kernel form the launch rules choose (fa_host::select_launch);
+// the broadcast is its own launch after the reduce
+hipError_t run_default(const fa_plan* plan, ReduceArgs& a, int n, bool weighted, bool bcast,
+                       hipStream_t st) {
+  const fa_host::Launch L = fa_host::select_launch(*plan, n, weighted, kernel_slots);
+  a.tiles = L.table >= 0 ? plan->d_bal[L.table] : L.alt ? plan->d_tiles_alt : plan->d_tiles;
+  a.sidx = L.alt && plan->d_sidx ? plan->d_sidx + plan->sidx_alt_off : plan->d_sidx;
+  a.nscalar = L.ns;
+  a.ntiles = L.nt;
+  hipError_t e = launch_reduce(a, L.nt, L.vec_u, st, L.batch, L.pipe);
+  if (e == hipSuccess && bcast) e = launch_bcast(plan, a, n, L.nt, st);
+  return e;
+}
+}  // namespace
+
 int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* const* c64, int n,
                   const float* weights, void* ctable, float* out32, int64_t* out64,
                   unsigned flags, void* stream) {
@@ -2353,7 +1626,8 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
     return set_err(FA_E_RANGE, "fa_reduce: n=%d exceeds FA_MAX_CLIENTS=%d", n, FA_MAX_CLIENTS);
   if (flags & ~(FA_F_BCAST | FA_F_SUM_ONLY | FA_F_BCAST_ONLY))
     return set_err(FA_E_INVAL, "fa_reduce: bad flags");
-  if (plan->order == FA_ORDER_TORCH_GPU && weights)
+  const bool tgpu = plan->order == FA_ORDER_TORCH_GPU;
+  if (tgpu && weights)
     return set_err(FA_E_INVAL, "fa_reduce: the torch-GPU order is the reference's unweighted mean");
   const bool h16 = plan->elem != FA_ELEM_F32;
   if (h16 && (flags & FA_F_SUM_ONLY))
@@ -2363,7 +1637,6 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
     return set_err(FA_E_INVAL, "fa_reduce: a 16-bit plan broadcasts the bucket's bytes flat (a "
                                "mixed plan: narrows the whole fp32 bucket) and needs "
                                "FA_PLAN_GAPS_ARE_PADDING with full coverage");
-  const fa_plan_info& in = plan->info;
   if (plan->info.ntiles == 0) return FA_OK;
   ReduceArgs a;
   memset(&a, 0, sizeof a);
@@ -2372,7 +1645,9 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
   a.out64 = out64;
   a.n = n;
   a.n_total = n;
-  a.flags = flags | (weights ? 0x100u : 0u);
+  // every reduce's broadcast is a launch of its own: FA_F_BCAST reaches the
+  // kernels through launch_bcast only
+  a.flags = (flags & ~FA_F_BCAST) | (weights ? 0x100u : 0u);
   const bool need32 = plan->has32, need64 = plan->has64;
   if (need32) {
     if (!c32 || !out32) return set_err(FA_E_INVAL, "fa_reduce: fp32 buckets required");
@@ -2393,134 +1668,31 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
   if (dev != plan->device)
     return set_err(FA_E_INVAL, "fa_reduce: plan built on device %d, current device %d",
                    plan->device, dev);
+  const bool bcast_only = (flags & FA_F_BCAST_ONLY) != 0, bcast = (flags & FA_F_BCAST) != 0;
   hipStream_t st = (hipStream_t)stream;
-  void* table = nullptr;
-  if (n <= kInline) {
-    for (int i = 0; i < n; ++i) {
-      if (need32) a.c32[i] = c32[i];
-      if (need64) a.c64[i] = c64[i];
-      if (weights) a.w[i] = weights[i];
-    }
+  ClientTable tab{st};
+  hipError_t e = tab.fill(a, need32 ? c32 : nullptr, need64 ? c64 : nullptr, n, weights, ctable);
+  if (e != hipSuccess)
+    return set_err(FA_E_HIP, "fa_reduce: client pointer table: %s", hipGetErrorString(e));
+  if (tgpu && !bcast_only && n != plan->order_n)
+    return set_err(FA_E_INVAL, "fa_reduce: torch-GPU-order plan cut for n=%d, called with n=%d",
+                   plan->order_n, n);
+  const char* what;
+  if (bcast_only) {
+    what = "broadcast launch";
+    e = run_bcast_only(plan, a, n, st);
+  } else if (tgpu) {
+    what = "torch-GPU-order launch";
+    e = run_tgpu(plan, a, n, bcast, st);
+  } else if (h16) {
+    what = "16-bit reduce launch";
+    e = run_h16(plan, a, n, weights != nullptr, bcast, st);
   } else {
-    // [n fp32 ptrs][n int64 ptrs][n weights], stream-ordered alloc + copy
-    std::vector<char> host((size_t)n * 20);
-    const void** h32 = (const void**)host.data();
-    const void** h64 = h32 + n;
-    float* hw = (float*)(h64 + n);
-    for (int i = 0; i < n; ++i) {
-      h32[i] = need32 ? (const void*)c32[i] : nullptr;
-      h64[i] = need64 ? (const void*)c64[i] : nullptr;
-      hw[i] = weights ? weights[i] : 0.f;
-    }
-    if (ctable) {   // caller-owned (fa_reduce_tab): written by kernels, no memcpy
-      a.tab32 = (const float* const*)ctable;
-      a.tab64 = (const int64_t* const*)((const void**)ctable + n);
-      a.tabw = (const float*)((const void**)ctable + 2 * n);
-      HIP_TRY(table_fill(ctable, host, st));
-    } else {
-      HIP_TRY(table_alloc(&table, host.size(), st));
-      HIP_TRY(hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, st));
-      a.tab32 = (const float* const*)table;
-      a.tab64 = (const int64_t* const*)((const void**)table + n);
-      a.tabw = (const float*)((const void**)table + 2 * n);
-    }
+    what = "reduce launch";
+    e = run_default(plan, a, n, weights != nullptr, bcast, st);
   }
-  if (flags & FA_F_BCAST_ONLY) {
-    // the broadcast alone (the reference's initial sync, train_fedavg.py:
-    // 244-250, and :148-149 without the reduce): out32/out64 -> every client
-    const int nt = plan->order == FA_ORDER_TORCH_GPU ? in.ntiles : plan->nt_dev;
-    a.ntiles = nt;
-    a.sidx = plan->d_sidx;
-    hipError_t e = launch_bcast(plan, a, n, nt, st);
-    if (table) {
-      hipError_t e2 = hipFreeAsync(table, st);
-      if (e == hipSuccess) e = e2;
-    }
-    if (e != hipSuccess) return set_err(FA_E_HIP, "broadcast launch: %s", hipGetErrorString(e));
-    return FA_OK;
-  }
-  if (plan->order == FA_ORDER_TORCH_GPU) {
-    if (n != plan->order_n) {
-      if (table) (void)hipFreeAsync(table, st);
-      return set_err(FA_E_INVAL, "fa_reduce: torch-GPU-order plan cut for n=%d, called with n=%d",
-                     plan->order_n, n);
-    }
-    hipError_t e = hipSuccess;
-    // the broadcast as its own launch over the whole table, client groups
-    // per tile (as the default order's split broadcast)
-    const bool bc = (flags & FA_F_BCAST) != 0;
-    a.flags &= ~FA_F_BCAST;
-    for (int g = 0; g < 5 && e == hipSuccess; ++g) {
-      const int lo = plan->tg_lo[g], cnt = plan->tg_lo[g + 1] - lo;
-      if (cnt == 0) continue;
-      a.tiles = plan->d_tiles + lo;
-      a.tfac = plan->d_fac + lo;
-      a.ntiles = cnt;
-      switch (g) {
-        case 0:
-          // the client loop on full tiles at every N (r05,
-          // profiles/r05_ab_lib_tgpu_client_loop.jsonl)
-          if (plan->tgpu_batch == 8)
-            hipLaunchKernelGGL((tgpu_kernel<0, 8, 1>), dim3(cnt), dim3(kBlock), 0, st, a);
-          else
-            hipLaunchKernelGGL((tgpu_kernel<0, 16, 1>), dim3(cnt), dim3(kBlock), 0, st, a);
-          break;
-        case 1:
-          hipLaunchKernelGGL(tgpu_kernel<1>, dim3(cnt), dim3(kBlock), plan->tgpu_s2_lds, st, a);
-          break;
-        case 2: hipLaunchKernelGGL(tgpu_kernel<2>, dim3(cnt), dim3(kBlock), 0, st, a); break;
-        case 3: hipLaunchKernelGGL(tgpu_kernel<3>, dim3(cnt), dim3(kBlock), 0, st, a); break;
-        default: hipLaunchKernelGGL(tgpu_kernel<4>, dim3(cnt), dim3(kBlock), 0, st, a); break;
-      }
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess && bc && plan->tg_lo[5] > 0) {
-      a.tiles = plan->d_tiles;
-      a.ntiles = plan->tg_lo[5];
-      e = launch_bcast(plan, a, n, a.ntiles, st);
-    }
-    if (table) {
-      hipError_t e2 = hipFreeAsync(table, st);
-      if (e == hipSuccess) e = e2;
-    }
-    if (e != hipSuccess) return set_err(FA_E_HIP, "torch-GPU-order launch: %s", hipGetErrorString(e));
-    return FA_OK;
-  }
-  if (h16) {
-    // the 16-bit kernels (fedagg_h16.hip) over the plan's one table, then the
-    // broadcast's flat copy of the result bucket
-    a.nscalar = plan->ns_dev;
-    a.sidx = plan->d_sidx;
-    a.ntiles = plan->nt_dev;
-    const bool bc = (flags & FA_F_BCAST) != 0;
-    a.flags &= ~FA_F_BCAST;
-    hipError_t e = fa_h16::launch(a, plan->nt_dev, plan->elem, plan->vec_u, weights != nullptr,
-                                  plan->out_elem == FA_ELEM_F32, st);
-    if (e == hipSuccess && bc) e = launch_bcast(plan, a, n, plan->nt_dev, st);
-    if (table) {
-      hipError_t e2 = hipFreeAsync(table, st);
-      if (e == hipSuccess) e = e2;
-    }
-    if (e != hipSuccess) return set_err(FA_E_HIP, "16-bit reduce launch: %s", hipGetErrorString(e));
-    return FA_OK;
-  }
-  const Launch L = select_launch(plan, n, weights != nullptr, flags);
-  a.tiles = L.tiles;
-  a.nscalar = L.ns;
-  a.sidx = L.sidx;
-  const int ntiles = L.nt, vec_u = L.vec_u;
-  a.ntiles = ntiles;
-  // the broadcast is its own launch after the reduce
-  const bool bcast = (flags & FA_F_BCAST) != 0;
-  a.flags &= ~FA_F_BCAST;
-  hipError_t e = launch_reduce(a, ntiles, vec_u, plan->flags, st, L.batch,
-                               pipe_rule(plan, L, n, weights != nullptr));
-  if (e == hipSuccess && bcast) e = launch_bcast(plan, a, n, ntiles, st);
-  if (table) {
-    hipError_t e2 = hipFreeAsync(table, st);
-    if (e == hipSuccess) e = e2;
-  }
-  if (e != hipSuccess) return set_err(FA_E_HIP, "reduce launch: %s", hipGetErrorString(e));
+  e = tab.done(e);
+  if (e != hipSuccess) return set_err(FA_E_HIP, "%s: %s", what, hipGetErrorString(e));
   return FA_OK;
 }
 
@@ -2597,34 +1769,13 @@ int fa_reduce_chain(const fa_plan* plan, const float* const* c32, int n, const f
   a.lev_out = (int)lout;
   a.plane = ch->plane;
   a.flags = flags | (weights ? 0x100u : 0u);
-  a.ntiles = plan->nt_dev;
+  a.ntiles = plan->nt;
   hipStream_t s = (hipStream_t)stream;
-  void* table = nullptr;
-  if (n <= kInline) {
-    for (int i = 0; i < n; ++i) {
-      a.c32[i] = c32[i];
-      if (weights) a.w[i] = weights[i];
-    }
-  } else {
-    std::vector<char> host((size_t)n * 20);
-    const void** h32 = (const void**)host.data();
-    float* hw = (float*)(h32 + 2 * n);
-    for (int i = 0; i < n; ++i) {
-      h32[i] = c32[i];
-      h32[n + i] = nullptr;
-      hw[i] = weights ? weights[i] : 0.f;
-    }
-    HIP_TRY(table_alloc(&table, host.size(), s));
-    HIP_TRY(hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, s));
-    a.tab32 = (const float* const*)table;
-    a.tab64 = (const int64_t* const*)((const void**)table + n);
-    a.tabw = (const float*)((const void**)table + 2 * n);
-  }
-  hipError_t e = launch_chain(a, a.ntiles, plan->vec_u, s);
-  if (table) {
-    hipError_t e2 = hipFreeAsync(table, s);
-    if (e == hipSuccess) e = e2;
-  }
+  ClientTable tab{s};
+  hipError_t e = tab.fill(a, c32, nullptr, n, weights, nullptr);
+  if (e != hipSuccess)
+    return set_err(FA_E_HIP, "fa_reduce_chain: client pointer table: %s", hipGetErrorString(e));
+  e = tab.done(launch_chain(a, a.ntiles, plan->vec_u, s));
   if (e != hipSuccess) return set_err(FA_E_HIP, "chain launch: %s", hipGetErrorString(e));
   return FA_OK;
 }

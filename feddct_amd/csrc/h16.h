@@ -8,11 +8,7 @@
 #include "reduce_impl.h"
 
 namespace fa_h16 {
-// Elements of a vector tile per 16-B load per lane of the 256-thread
-// workgroup: a tile is u * kTile elements, u in {1, 2}.
-constexpr int kVec = 8;
-constexpr int kTile = kVec * fa_k::kBlock;  // 2048
-constexpr int kDefaultU = 1;                // 2048-element tiles: measured, DESIGN §4.8
+// (kVec, kTile, kDefaultU — the 16-bit tile widths — are in tiles.h)
 
 // One workgroup per tile of the table in `a` (packed scalar tiles first).
 // `a.c32[]` / `a.tab32[]` / `a.out32` carry the 16-bit bucket pointers.

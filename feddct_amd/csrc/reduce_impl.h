@@ -1,6 +1,8 @@
 // reduce_impl.h — the reduce kernel family of libfedagg.so (torch's CPU
 // summation order over flat client buckets, fedagg.hip's header comment) and
-// its launchers.  Shared by fedagg.hip (plans, C ABI, every other kernel)
+// its launchers.  Shared by fedagg.hip (plan upload, C ABI, every other
+// kernel; the tile planners and launch rules are host code, plan_host.cpp,
+// and the tile types they share with the kernels are in tiles.h)
 // and the fedagg_k*.hip translation units, which instantiate the launcher
 // templates for disjoint (tile width U, client batch B) sets so hipcc builds
 // the reduce_kernel variants in parallel; fedagg.hip declares those
@@ -18,53 +20,9 @@
 #include <cstdint>
 
 #include "common.h"
+#include "tiles.h"
 
 namespace fa_k {
-
-// ----------------------------------------------------------------- tiles --
-enum TileKind : int32_t {
-  K_F32_VEC = 0,      // cascade order, 16-B vectors, count % 4 == 0
-  K_F32_CASC_S = 1,   // cascade order, one element per thread (unaligned)
-  K_F32_ILP4 = 2,     // tail columns: ILP-4 order
-  K_F32_INNER = 3,    // M == 1: ILP-4 (n < 8) or 8-lane inner (n >= 8)
-  K_I64_CASC = 4,
-  K_I64_ILP4 = 5,
-  K_I64_INNER = 6,
-  // torch-ROCm's GPU order (fa_plan_create_order, FA_ORDER_TORCH_GPU); the
-  // tile's kind carries log2 of its stride in bits 8-15
-  K_F32_TGPU = 7,     // [N, M>=2]: S-way row split, 4 round-robin accumulators
-  K_I64_TGPU = 8,
-  K_F32_TGPU_IN = 9,  // M == 1: lane split + intra-wave shuffle tree, 1 element/wave
-  K_I64_TGPU_IN = 10,
-  K_F32_TGPU_V = 11,  // [N, M>=2], 16-B aligned run: 4 elements per lane, up to 1024
-  K_F32_TGPU_W = 12,  // the same with S = 1: 8 elements per lane (2 x 16 B), up to 2048
-  // device tables only (r03): the plan's scalar tiles (kinds 1-6) packed,
-  // up to 256 elements of any tensors per tile; `start` indexes the plan's
-  // scalar index, whose entries are (bucket element << 4) | kind
-  K_SCALAR_PACKED = 13,
-};
-
-__host__ __device__ inline bool kind_is64(int kind) {
-  const int b = kind & 0xFF;
-  return b == K_I64_CASC || b == K_I64_ILP4 || b == K_I64_INNER || b == K_I64_TGPU ||
-         b == K_I64_TGPU_IN;
-}
-
-struct Tile {
-  int64_t start;  // first element (bucket index)
-  int32_t count;  // elements
-  int32_t kind;
-};
-static_assert(sizeof(Tile) == 16, "tile is 16 B");
-
-constexpr int kBlock = 256;
-constexpr int kDefaultU = 2;
-// MI355X's device properties as torch-ROCm's setReduceConfig reads them
-// (multiProcessorCount, maxThreadsPerMultiProcessor): they decide where torch
-// splits a reduction across blocks (fa_torch_gpu_config); a GPU test checks
-// them against torch.cuda.get_device_properties.
-constexpr int64_t kTorchNumCU = 256;
-constexpr int64_t kTorchMaxThreadsPerCU = 2048;  // float4 vectors per thread per client (tools/tune.py)
 
 constexpr int kInline = FA_INLINE_CLIENTS;
 
@@ -360,7 +318,7 @@ __device__ __forceinline__ void batch_tail(KArgs& a, Acc<U, DEEP>& A, int b0, in
 // form, but the adds, the promotion and the next pointer's scalar load no
 // longer sit between one client's data arriving and the next client's loads
 // leaving.  Its own kernel instances (PIPE), full tiles only; the launch
-// rule (fedagg.hip pipe_rule) and the measurements behind it are in DESIGN
+// rule (plan_host.cpp pipe_rule) and the measurements behind it are in DESIGN
 // §4.1: 1.0-1.7 % faster for 2..7 and 17..63 clients (r06: 12..63, and
 // unweighted 64..128), mean or weighted, in
 // launches of three or more rounds (cfg2, cfg3, cfg4, cfg5), slower for
@@ -404,7 +362,7 @@ __device__ __forceinline__ void pipe2_clients(KArgs& a, Acc<U, DEEP>& A, int n, 
   }
 }
 
-// PIPE (r05): pipe2_clients for the full tiles (fedagg.hip pipe_rule); its
+// PIPE (r05): pipe2_clients for the full tiles (plan_host.cpp pipe_rule); its
 // own kernel instances, so the other kernels' code is unchanged
 template <int U, int B, bool FULL, bool DEEP, bool WEIGHTED, int POL, bool CHAIN, int PIPE = 0>
 __device__ __forceinline__ void tile_vec(KArgs& a, int64_t start,
@@ -629,7 +587,7 @@ __device__ __forceinline__ void scalar_column(KArgs& a, const SrcF& sf, const Sr
 // and each lane loads its column's value), 8 rows in flight per lane; then
 // wave 0 runs every column's order from LDS.  More rows than fit
 // kStageFloats / kPackCols: the columns in sub-batches of kStageFloats / N.
-constexpr int kPackCols = 64;
+// (kPackCols: tiles.h)
 
 // Packed tile k's entries sit at sidx[k * kPackCols, +kPackCols) (unused
 // slots -1), so a scalar workgroup needs no tile descriptor: its first load
@@ -725,7 +683,7 @@ hipError_t launch_chain_ub(const ReduceArgs& a, int ntiles, bool deep, bool w, h
   return w ? launch_one<U, B, false, true, 3, true>(a, ntiles, st)
            : launch_one<U, B, false, false, 3, true>(a, ntiles, st);
 }
-// The reduce: nt loads, sc1 result stores (POL 5, st_out).  pipe (fedagg.hip
+// The reduce: nt loads, sc1 result stores (POL 5, st_out).  pipe (plan_host.cpp
 // pipe_rule; U = 2 only): 1 the PIPE instances over the inline pointers (not
 // deep), 2 (r06) the unweighted DEEP instance over the pointer table.
 template <int U, int B>
@@ -748,7 +706,7 @@ hipError_t launch_u(const ReduceArgs& a, int ntiles, bool deep, bool w, int pipe
 
 // Resident workgroups per CU of launch_u<U, B>'s kernel for this call
 // shape; 0 if the runtime cannot say.  The
-// plan cuts its balanced tile tables for these counts (fedagg.hip).
+// plan cuts its balanced tile tables for these counts (plan_host.cpp plan_tables).
 template <int U, int B>
 int occupancy_u(bool deep, bool w) {
   int nb = 0;

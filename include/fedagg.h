@@ -49,6 +49,7 @@
 #ifndef FEDAGG_H
 #define FEDAGG_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus

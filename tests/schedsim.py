@@ -49,7 +49,7 @@ USER_KERNELS = {"K_SUM", "K_ZERO", "K_STACK", "K_PART", "K_BLOCK", "K_SCALE", "K
 
 
 def _column_sum(kind, rows):
-    """Per-column order of a tile kind (fedagg.hip TileKind) over rows (list
+    """Per-column order of a tile kind (csrc/tiles.h TileKind) over rows (list
     of equal 1-D arrays)."""
     if kind in (0, 1):
         return O.cascade(rows)

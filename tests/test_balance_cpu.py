@@ -4,7 +4,7 @@ them is the same per-column order), stay within the kernel's tile width, sit
 on 64-element lines, and with the packed scalar tiles fill the one round of
 the slot count they part-fill — or the plain cut is kept when that round is
 >= 97 % full or the launch needs more than one round (measured: re-cutting a
-multi-round launch is slower, fedagg.hip balance_vec), except that a
+multi-round launch is slower, plan_host.cpp balance_vec), except that a
 multi-round launch spilling 0 < r <= 0.44 slots tiles past its last full
 round (the measured range, r04) has its last slots - r tiles split in halves
 (split_tail, r03 session 4).

@@ -5,7 +5,7 @@ workgroups runs a table re-cut to fill it; one that needs two rounds of the
 one that spills r <= 0.44 slots tiles past its last full round has its last
 slots - r tiles split in halves (session 4, split_tail; at N < 16 too, on
 the 8-client kernels' slots); everything else
-runs the plain table (fedagg.hip balance_vec / round_batch).
+runs the plain table (plan_host.cpp balance_vec / round_batch).
 Each call here runs once through the plan's choice and once through the
 plain table with the default batch (FA_PLAN_TUNE_NO_BALANCE): the results
 must be the same bits, and the launch shape must be the one the rule names.
@@ -94,7 +94,7 @@ def test_balanced_table_same_bits(lib, name, n, weighted):
     nt_b, slots = pb.launch_shape(n, weighted)
     nt_p, slots_p = pp.launch_shape(n, weighted)   # the default batch's slots
     assert slots > 0 and slots_p > 0 and slots % 256 == 0
-    # the 16-client kernels from B16 clients (r06: 12; fedagg.hip pick_batch)
+    # the 16-client kernels from B16 clients (r06: 12; plan_host.cpp pick_batch)
     s8 = pp.launch_shape(5, weighted)[1] if n >= B16 else slots_p
     k = -(-nt_p // slots_p)
     r = nt_p - (k - 1) * slots_p

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a libfedagg.so variant for tools/ab_lib.py: every unit of the library
-# recompiled with extra -D flags (the launch rules live in fedagg.hip, the
+# recompiled with extra -D flags (the launch rules live in plan_host.cpp, the
 # kernel instances in fedagg_k*.hip).  Run HERE (CPU); the .so travels to the
 # box with the tree (tools/*.so is git-ignored only).
 #   bash tools/lib_variant.sh TAG -DFA_TGPU_LOOP_DEPTH=2 ...
