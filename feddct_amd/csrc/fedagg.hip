@@ -1637,6 +1637,8 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
     return set_err(FA_E_INVAL, "fa_reduce: a 16-bit plan broadcasts the bucket's bytes flat (a "
                                "mixed plan: narrows the whole fp32 bucket) and needs "
                                "FA_PLAN_GAPS_ARE_PADDING with full coverage");
+  if (n > kInline && ctable && ((uintptr_t)ctable & 7))
+    return set_err(FA_E_ALIGN, "fa_reduce_tab: table not 8-B aligned");
   if (plan->info.ntiles == 0) return FA_OK;
   ReduceArgs a;
   memset(&a, 0, sizeof a);
@@ -1669,14 +1671,15 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
     return set_err(FA_E_INVAL, "fa_reduce: plan built on device %d, current device %d",
                    plan->device, dev);
   const bool bcast_only = (flags & FA_F_BCAST_ONLY) != 0, bcast = (flags & FA_F_BCAST) != 0;
+  // refused before the table is filled: no refusal launches or allocates
+  if (tgpu && !bcast_only && n != plan->order_n)
+    return set_err(FA_E_INVAL, "fa_reduce: torch-GPU-order plan cut for n=%d, called with n=%d",
+                   plan->order_n, n);
   hipStream_t st = (hipStream_t)stream;
   ClientTable tab{st};
   hipError_t e = tab.fill(a, need32 ? c32 : nullptr, need64 ? c64 : nullptr, n, weights, ctable);
   if (e != hipSuccess)
     return set_err(FA_E_HIP, "fa_reduce: client pointer table: %s", hipGetErrorString(e));
-  if (tgpu && !bcast_only && n != plan->order_n)
-    return set_err(FA_E_INVAL, "fa_reduce: torch-GPU-order plan cut for n=%d, called with n=%d",
-                   plan->order_n, n);
   const char* what;
   if (bcast_only) {
     what = "broadcast launch";

@@ -282,7 +282,10 @@ int fa_plan_create_order(const fa_seg *seg32, int nseg32, int64_t f32_numel,
  *                      ordered sum of fp32(x_i * w_i) (no division)
  *   out32 / out64    : global buckets (may alias a client bucket)
  *   flags            : FA_F_BCAST | FA_F_SUM_ONLY, or FA_F_BCAST_ONLY
- * int64 keys always take the mean + truncation path (weights ignored). */
+ * int64 keys always take the mean + truncation path (weights ignored): every
+ * int64 value is rounded to nearest-even into fp32, as .float() rounds it.
+ * The result is unspecified where the fp32 mean is NaN or outside int64's
+ * range (2^63 and beyond in magnitude; -2^63 itself is inside). */
 int fa_reduce(const fa_plan *plan, const float *const *c32,
               const int64_t *const *c64, int n, const float *weights,
               float *out32, int64_t *out64, unsigned flags, void *stream);
@@ -295,7 +298,10 @@ int fa_reduce(const fa_plan *plan, const float *const *c32,
  * no allocation and no host copy, so the call can be captured into a HIP
  * graph (hipStreamBeginCapture) and replayed.  `table` must stay allocated
  * and untouched while any launch or graph replay that uses it can run.
- * table may be NULL when n <= FA_INLINE_CLIENTS. */
+ * table may be NULL when n <= FA_INLINE_CLIENTS (it is not looked at then);
+ * above, a table that is not 8-B aligned is refused with FA_E_ALIGN, and a
+ * NULL table is fa_reduce's pool path (not capturable).  Every refusal
+ * returns before anything is launched: the table is not written. */
 size_t fa_table_bytes(int n);
 int fa_reduce_tab(const fa_plan *plan, const float *const *c32,
                   const int64_t *const *c64, int n, const float *weights,
@@ -346,7 +352,8 @@ int fa_mean_i64_trunc(const int64_t *const *clients, int n, int64_t numel,
                       void *stream);
 
 /* Elementwise out[j] = x[j] / d (IEEE true division), fp32; and the int64
- * finish of a cross-GPU partial sum: out64[j] = trunc(x[j] / d). */
+ * finish of a cross-GPU partial sum: out64[j] = trunc(x[j] / d), unspecified
+ * where the quotient is NaN or outside int64's range. */
 int fa_div_f32(const float *x, float d, float *out, int64_t numel,
                void *stream);
 int fa_div_trunc_i64(const float *x, float d, int64_t *out, int64_t numel,

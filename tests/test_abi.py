@@ -47,6 +47,25 @@ def test_version_and_error_paths():
         _lib.build_tiles_host(np.array([[0, 10], [5, 10]]), 20)
 
 
+def test_table_bytes_and_reduce_tab_null_plan():
+    """fa_table_bytes: nothing up to FA_INLINE_CLIENTS; above, room for n
+    fp32 pointers, n int64 pointers and n weights (20 n bytes) in whole 8-B
+    words.  fa_reduce_tab refuses a NULL plan before it looks at anything
+    else."""
+    L = _lib.lib
+    for n in (-1, 0, 1, 127, _lib.FA_INLINE_CLIENTS):
+        assert L.fa_table_bytes(n) == 0, n
+    for n in (129, 160, 161, 65536):
+        b = L.fa_table_bytes(n)
+        assert b % 8 == 0 and b >= 20 * n, (n, b)
+        assert b < 20 * n + 8, (n, b)
+    assert L.fa_reduce_tab(None, None, None, 1, None, None, None, None, 0,
+                           None) == _lib.FA_E_INVAL
+    assert b"NULL" in L.fa_last_error()
+    assert L.fa_reduce_tab(None, None, None, 129, None, ctypes.c_void_p(4), None, None, 0,
+                           None) == _lib.FA_E_INVAL
+
+
 def _expected_kind(M, col):
     """Which torch order an element uses (oracle column rule)."""
     if M == 1:
