@@ -264,11 +264,11 @@ def test_native_chained_weighted(comm):
 @pytest.mark.parametrize("final", ["reduce", "allreduce"])
 @pytest.mark.parametrize("n,weighted", [(20, False), (5, False), (300, False), (33, True)])
 def test_native_blocked_one_rank_is_bit_exact(comm, lay, final, n, weighted):
-    """fa_reduce_blocked on a real RCCL communicator with one rank: every
-    block is local (fa_reduce per 16 slots), the rank owns the one stripe and
-    folds the block sums with the cascade's promotions (n=300: level 2) —
-    the single-GPU reduction bit for bit.  Multi-rank: tests/test_schedule.py
-    (CPU replay) and tests/test_gpu_loopback.py (2..8 ranks on this GPU)."""
+    """fa_reduce_blocked on a real RCCL communicator with one rank: the
+    single-GPU reduction bit for bit.  (Since r04 a one-rank plan runs no
+    block sums and no fold: its round is one fa_reduce over all the slots.)
+    The blocks and the fold: tests/test_schedule.py (CPU replay) and
+    tests/test_gpu_loopback.py (2..8 ranks on this GPU)."""
     from feddct_amd.comm import NativeBlockedAggregator
     man = load_manifest(lay)
     layout = BucketLayout.from_manifest(man)
@@ -287,6 +287,89 @@ def test_native_blocked_one_rank_is_bit_exact(comm, lay, final, n, weighted):
     assert torch.equal(torch.isnan(out32[mask]), nan)
     assert torch.equal(out32[mask].view(torch.int32)[~nan], want32[mask].view(torch.int32)[~nan])
     assert torch.equal(out64, want64)
+
+
+# ---- the blocked entry at N >= 4096 (256 and more cascade blocks) ----
+# A small layout with every column class of the round: several vector
+# tiles (a full 4096-float run, 2048 + 8, partial ones), ILP-4 tails, a 0-d
+# fp32 key and an int64 key, ~7.5 k floats, so thousands of clients stay cheap.
+DEEP_MAN = {"name": "deep", "keys": [
+    {"key": "a.weight", "shape": [37, 3], "dtype": "float32"},
+    {"key": "s", "shape": [], "dtype": "float32"},
+    {"key": "b.weight", "shape": [4101], "dtype": "float32"},
+    {"key": "c.bias", "shape": [2048 + 8], "dtype": "float32"},
+    {"key": "n1", "shape": [], "dtype": "int64"},
+    {"key": "d.weight", "shape": [100], "dtype": "float32"},
+    {"key": "e.weight", "shape": [1030], "dtype": "float32"}]}
+DEEP_MAX = 8500
+_deep = {}
+
+
+def _deep_clients():
+    """DEEP_MAX adversarial clients of DEEP_MAN, made once (every case takes a
+    prefix), and their buckets on the host for the CPU oracle."""
+    if "clients" not in _deep:
+        torch.cuda.set_device(DEV)
+        layout = BucketLayout.from_manifest(DEEP_MAN)
+        clients = make_clients(layout, DEEP_MAN, range(DEEP_MAX), DEV, mode=synth.MODE_ADVERSARIAL)
+        h32 = torch.stack([c[0] for c in clients]).cpu().numpy()
+        h64 = torch.stack([c[1] for c in clients]).cpu().numpy()
+        _deep["clients"] = (layout, clients, h32, h64)
+    return _deep["clients"]
+
+
+def _deep_oracle(n, weighted):
+    """The oracle's result for the first n clients, from the host copies of
+    their buckets: independent of the library."""
+    from oracle import torch_order as O
+    key = (n, weighted)
+    if key not in _deep:
+        layout, _, h32, h64 = _deep_clients()
+        w = O.weights_from_sizes(np.arange(1, n + 1) * 7 + 3) if weighted else None
+        want = {}
+        for s in layout.slots:
+            if s.kind == "i64":
+                x = h64[:n, s.offset:s.offset + s.numel].reshape((n,) + tuple(s.shape))
+                want[s.key] = O.mean_i64_trunc(x)
+            else:
+                x = h32[:n, s.offset:s.offset + s.numel].reshape((n,) + tuple(s.shape))
+                want[s.key] = O.torch_mean0(x) if w is None else O.weighted_sum0(x, w)
+        _deep[key] = (w, want)
+    return _deep[key]
+
+
+@pytest.mark.parametrize("final", ["reduce", "allreduce"])
+@pytest.mark.parametrize("n,weighted", [(4096, False), (4097, False), (4097, True),
+                                        (4112, False), (8200, False), (8500, False)])
+def test_native_blocked_one_rank_deep(comm, final, n, weighted):
+    """fa_reduce_blocked on a real one-rank RCCL communicator at the client
+    counts where the blocked round's fold changes form (256 pieces at
+    N = 4096, 257 at 4097 and 4112, 513 at 8200, 532 with open levels 1 and 2
+    at 8500): one GPU's reduction and the CPU oracle's result, bit for bit.
+    A one-rank plan runs NO blocks and no fold — its round is one fa_reduce
+    over all the slots (fedcomm.hip, `single`) — so this pins that entry and
+    its pointer tables at depth; the fold itself at these piece counts runs
+    across ranks in tests/test_gpu_loopback.py test_loopback_deep_cascade."""
+    from feddct_amd.comm import NativeBlockedAggregator
+    layout, clients, _, _ = _deep_clients()
+    clients = clients[:n]
+    w, want = _deep_oracle(n, weighted)
+    want32, want64 = _single_gpu(layout, clients, weights=w)
+    out32 = torch.full_like(clients[0][0], float("nan"))
+    out64 = torch.full_like(clients[0][1], -7)
+    agg = NativeBlockedAggregator(layout, [c[0] for c in clients], [c[1] for c in clients], n,
+                                  out32, out64, comm, final=final, weights=w)
+    for _ in range(2):
+        agg.step()
+    torch.cuda.synchronize()
+    mask = _layout_pad_mask(layout)
+    assert not torch.isnan(want32[mask]).any()
+    assert torch.equal(out32[mask].view(torch.int32), want32[mask].view(torch.int32))
+    assert torch.equal(out64, want64)
+    g32, g64 = out32.cpu().numpy(), out64.cpu().numpy()
+    for s in layout.slots:
+        got = (g64 if s.kind == "i64" else g32)[s.offset:s.offset + s.numel].reshape(s.shape)
+        assert got.tobytes() == np.asarray(want[s.key]).tobytes(), (n, s.key, "vs oracle")
 
 
 @pytest.mark.parametrize("final", ["reduce", "allreduce"])
@@ -360,9 +443,23 @@ def test_captured_rounds_replay_bit_exact(form, n):
     new capture, and every result equals the uncaptured executor's and one
     GPU's reduce, bit for bit — at 300 slots too, where the tails and the
     stripe take the graph's own device pointer tables."""
+    man = load_manifest("wrnsl16_8_sf4_c10_main" if n > 20 else "wrn16_8_c10")
+    _captured_rounds_replay(form, man, n)
+
+
+def test_captured_blocked_round_replays_past_256_pieces():
+    """The blocked entry at 4112 slots on the small deep layout, captured and
+    replayed: the same checks as above.  With one rank the captured round is
+    one fa_reduce over a 4112-row pointer table; the multi-rank round's 257
+    copies and its fold cannot be captured on one GPU (the loopback pairs
+    sends and receives on the host) and run uncaptured in
+    tests/test_gpu_loopback.py."""
+    _captured_rounds_replay("blocked", DEEP_MAN, 4112)
+
+
+def _captured_rounds_replay(form, man, n):
     from feddct_amd import comm as C
     torch.cuda.set_device(DEV)
-    man = load_manifest("wrnsl16_8_sf4_c10_main" if n > 20 else "wrn16_8_c10")
     layout = BucketLayout.from_manifest(man)
     clients = make_clients(layout, man, range(n), DEV, mode=synth.MODE_ADVERSARIAL)
     l32, l64 = [c[0] for c in clients], [c[1] for c in clients]

@@ -151,6 +151,46 @@ def test_loopback_small_layout_all_modes(tmp_path):
     _run(_small_layout(), cases, tmp_path)
 
 
+def _deep_layout():
+    """_small_layout() with ``c`` cut to 6500 floats (~11 k floats in all):
+    every column class still there, thousands of clients stay cheap."""
+    return BucketLayout([("a", (37, 3), "float32"), ("s", (), "float32"),
+                         ("b", (4101,), "float32"), ("t", (), "float32"),
+                         ("c", (6500,), "float32"), ("d", (3,), "float32"),
+                         ("e", (193,), "float32"), ("n1", (), "int64"),
+                         ("f", (65, 65), "float32"), ("n2", (), "int64")])
+
+
+DEEP_CASES = [
+    "blocked:2:250,10:0:threads:0:0",          # the spanning block ends at 256: CONT plane 2
+    "blocked:2:250,10:-1:single:1:0",
+    "blocked:2:4090,10:0:threads:0:0",         # ... at 4096: CONT plane 3; 257 pieces, copied
+    "blocked:2:4090,6:-1:threads:1:0",         # N = 4096: finishing continuation, 256 pieces
+    "blocked:3:4090,4110,30:-1:threads:0:0",   # N = 8230: 515 pieces, l3 twice, three owners
+    "chained:2:4096,5:1:threads:0:3",          # plane 3 alone crosses the hop
+    "chained:3:4090,4110,30:-1:threads:1:4",
+    "striped:2:4090,10:-1:threads:1:2",        # K_SCALE / the stacks in 64 launches of 64 rows
+    "multi:3:4090,4110,30:0:threads:0:0",      # whatever the cost model picks stays exact
+    # a one-rank communicator runs no fold (its round is one fa_reduce), so the
+    # fold's piece counts around kFoldPtrs = 256 are all pinned here
+    "blocked:2:4090,22:0:threads:0:0",         # N = 4112: 257 whole blocks, no remainder
+    "blocked:2:4090,7:-1:threads:1:0",         # N = 4097 weighted: 257 pieces, a one-row remainder
+    "blocked:2:4096,16:1:single:0:0",          # no spanning block: 257 local block sums
+    "blocked:2:4090,310:-1:single:0:0",        # N = 4400: levels 1 and 2 open over one l3 promotion
+]
+
+
+@pytest.mark.parametrize("part", [0, 1, 2])
+def test_loopback_deep_cascade(tmp_path, part):
+    """N >= 4096 across ranks: the chain state's fourth plane over a hop, the
+    blocked round's continuation planes 2 and 3, the owners' folds of 256
+    pieces (read where they lie), of 257 (copied into the fold's rows, with
+    and without a remainder) and of 515 (two level-3 promotions), the scale /
+    stack kernels in 64 launches.  In three driver runs, so that none waits
+    on thousands of client allocations for long."""
+    _run(_deep_layout(), DEEP_CASES[part::3], tmp_path, timeout=300)
+
+
 def test_loopback_cfg3_layout(cfg3_layout, tmp_path):
     """BASELINE config 3's joint FedDCT bucket (main + proxy, 11.0 M floats),
     5 client slots over 2..5 ranks."""

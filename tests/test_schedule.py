@@ -305,7 +305,8 @@ def test_deadlock_is_detected():
 
 
 BLOCK_COUNTS = [[20], [10, 10], [7, 0, 13], [16, 16, 1], [20, 20, 20], [20] * 8,
-                [12, 9, 30, 0, 14, 8], [100, 156, 44]]
+                [12, 9, 30, 0, 14, 8], [100, 156, 44],
+                [250, 10]]    # the spanning block ends at 256: its sum sent and copied from CONT plane 2
 
 
 @pytest.mark.parametrize("counts", BLOCK_COUNTS)
@@ -327,7 +328,8 @@ def test_blocked_schedule_is_exact(counts, root):
             assert got.tobytes() == np.asarray(want[s.key]).tobytes(), (r, s.key)
 
 
-@pytest.mark.parametrize("counts", [[10, 10], [20] * 8, [12, 9, 30, 0, 14, 8], [100, 156, 44]])
+@pytest.mark.parametrize("counts", [[10, 10], [20] * 8, [12, 9, 30, 0, 14, 8], [100, 156, 44],
+                                    [250, 10]])
 def test_blocked_schedule_weighted_is_exact(counts):
     layout, states, w, bufs, _ = _run(C.FA_MODE_BLOCKED, counts, -1, weighted=True)
     want = _expected(states, w)
@@ -356,6 +358,62 @@ def test_exact_schedules_beyond_4096_clients(mode, counts):
         src = bufs[0]["OUT64"] if s.kind == "i64" else bufs[0]["OUT"]
         got = src[s.offset:s.offset + s.numel].reshape(s.shape)
         assert got.tobytes() == np.asarray(want[s.key]).tobytes(), s.key
+
+
+# The counts the GPU loopback runs at depth (tests/test_gpu_loopback.py
+# test_loopback_deep_cascade), replayed here: a spanning block that ends on a
+# multiple of 256 / 4096 (its sum in CONT plane 2 / 3), N = 4096 exactly (the
+# spanning block is the last: a finishing continuation, 256 pieces), 257 and
+# 515 pieces, a chain hop that carries plane 3 alone.
+DEEP_CASES = [(C.FA_MODE_BLOCKED, [250, 10], 0), (C.FA_MODE_BLOCKED, [250, 10], -1),
+              (C.FA_MODE_BLOCKED, [4090, 10], 0), (C.FA_MODE_BLOCKED, [4090, 6], -1),
+              (C.FA_MODE_BLOCKED, [4090, 4110, 30], -1),
+              (C.FA_MODE_BLOCKED, [4090, 22], 0),     # 257 whole blocks, no remainder
+              (C.FA_MODE_BLOCKED, [4096, 16], 1),     # no spanning block: 257 local sums
+              (C.FA_MODE_CHAINED, [4096, 5], 1), (C.FA_MODE_CHAINED, [4090, 4110, 30], -1)]
+
+
+@pytest.mark.parametrize("mode,counts,root", DEEP_CASES)
+@pytest.mark.parametrize("weighted", [False, True])
+def test_deep_cascade_schedules_are_exact(mode, counts, root, weighted):
+    layout, states, w, bufs, scheds = _run(mode, counts, root, weighted=weighted, man=SMALL_MAN)
+    want = _expected(states, w)
+    for r in _result_ranks(len(counts), root):
+        for s in layout.slots:
+            src = bufs[r]["OUT64"] if s.kind == "i64" else bufs[r]["OUT"]
+            got = src[s.offset:s.offset + s.numel].reshape(s.shape)
+            assert got.tobytes() == np.asarray(want[s.key]).tobytes(), (r, s.key)
+    if mode == C.FA_MODE_CHAINED and counts == [4096, 5]:
+        sent = {x["src_index"] for x in scheds[0] if x["op"] == "SEND" and x["src"] == "STATE"}
+        assert sent == {3}
+
+
+@pytest.mark.parametrize("counts,plane", [([250, 10], 2), ([4090, 10], 3), ([4090, 6], 0)])
+def test_blocked_cont_planes(counts, plane):
+    """The holder of a spanning block leaves the block's sum in the CONT plane
+    the cascade's promotions at the block's last row name: a block ending on
+    a multiple of 256 in plane 2, of 4096 in plane 3, a finishing continuation
+    (the block ends the reduction) in plane 0 — and its sends to the owners
+    and its own copy into the fold's rows read that plane."""
+    holder = 1
+    # SMALL_MAN (the deep replay's layout) is one stripe, owned by rank 0: the
+    # holder sends; on MAN it owns a stripe too and copies its own part
+    for man, root in [(SMALL_MAN, 0), (SMALL_MAN, -1), (MAN, 0), (MAN, -1)]:
+        layout = BucketLayout.from_manifest(man)
+        ops = C.describe(C.FA_MODE_BLOCKED, layout, counts, holder, root=root)
+        cont = [x for x in ops if x["op"] == "K_CONT"]
+        assert len(cont) == 1 and cont[0]["dst"] == "CONT" and cont[0]["dst_index"] == plane
+        assert cont[0]["row0"] == counts[0] and cont[0]["nrows"] == 16 - counts[0] % 16
+        piece = counts[0] // 16
+        sends = [x for x in ops if x["op"] == "SEND" and x["src"] == "CONT"]
+        copies = [x for x in ops if x["op"] == "K_COPY" and x["src"] == "CONT"]
+        assert sends and all(x["step"] > cont[0]["step"] for x in sends + copies)
+        assert {x["src_index"] for x in sends} == {plane}
+        assert ([(x["src_index"], x["dst"], x["dst_index"]) for x in copies]
+                == ([(plane, "BLK", piece)] if man is MAN else []))
+        # the starter's side: no continuation, and nothing of its own in CONT
+        other = C.describe(C.FA_MODE_BLOCKED, layout, counts, 0, root=root)
+        assert not [x for x in other if x["op"] == "K_CONT" or x["src"] == "CONT"]
 
 
 @pytest.mark.parametrize("counts", [[4, 9, 0, 2, 5], [1, 1, 1, 17], [3] * 8])
