@@ -30,6 +30,7 @@ from __future__ import annotations
 import ctypes
 from typing import Sequence
 
+import numpy as np
 import torch
 
 from . import _lib, slab
@@ -90,8 +91,15 @@ class HostPipeline:
         n = len(host32)
         if n != self.n:
             raise ValueError(f"pipeline built for {self.n} clients, got {n}")
+        w = None
+        if weights is not None:
+            # (a ctypes array takes fewer initialisers than elements and
+            # zero-fills the rest: check the count, as Engine._weights_arg does)
+            wa = np.asarray(weights, np.float32).reshape(-1)
+            if wa.shape[0] != n:
+                raise ValueError(f"{wa.shape[0]} weights for {n} clients")
+            w = (ctypes.c_float * n)(*map(float, wa))
         compute = torch.cuda.current_stream(self.device)
-        w = None if weights is None else (ctypes.c_float * n)(*map(float, weights))
         # buffers of the previous round are free once its work is done
         self.s_in.wait_stream(compute)
         self.s_in.wait_stream(self.s_out)
