@@ -57,7 +57,7 @@ EXPORTS = [
     "fa_mean_i64_trunc", "fa_div_f32", "fa_div_trunc_i64", "fa_broadcast_f32",
     "fa_synth_fill_f32", "fa_synth_fill_i64", "fa_copy_f32",
     "fa_norm_plan_create", "fa_norm_plan_destroy", "fa_prox_norms", "fa_prox_grad",
-    "fa_prox_grad_ex",
+    "fa_prox_grad_ex", "fa_prox_norms_elem", "fa_prox_grad_elem",
     "fa_read_probe_f32", "fa_write_probe_f32", "fa_tune_prox_store", "fa_tune_prox_cpw", "fa_chain_levels", "fa_reduce_chain", "fa_torch_gpu_config",
     "fa_plan_create_order", "fa_table_bytes", "fa_reduce_tab",
     "fa_plan_balance_host", "fa_plan_launch_shape", "fa_plan_launch_form",
@@ -150,6 +150,9 @@ def _load():
         "fa_prox_norms": (_I, [_P, _P, _P, _P, _P, _P]),
         "fa_prox_grad": (_I, [_P, _P, _P, _P, _P, ctypes.c_float, _P, _P, _P]),
         "fa_prox_grad_ex": (_I, [_P, _P, _P, _P, _P, ctypes.c_float, _P, _P, ctypes.c_uint, _P]),
+        "fa_prox_norms_elem": (_I, [_P, _P, _I, _P, _I, _P, _P, _P]),
+        "fa_prox_grad_elem": (_I, [_P, _P, _I, _P, _I, _P, _P, ctypes.c_float, _P, _P,
+                                   ctypes.c_uint, _P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError = missing export: loud

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "common.h"
+#include "prox_plan.h"
 
 namespace {
 
@@ -312,7 +313,10 @@ struct fa_norm_plan {
   NormChunk* d_chunks = nullptr;
   int* d_seg_first = nullptr;
   float* d_partials = nullptr;
+  bool align8 = true;  // every segment offset a multiple of 8 elements (fa_prox_*_elem)
 };
+
+static_assert(sizeof(NormChunk) == sizeof(fa_prox::Chunk), "one chunk table for every element type");
 
 extern "C" {
 
@@ -323,12 +327,14 @@ int fa_norm_plan_create(const fa_seg* segs, int nseg, int64_t numel, fa_norm_pla
     return fa::set_err(FA_E_INVAL, "fa_norm_plan_create: bad segments");
   std::vector<NormChunk> ch;
   std::vector<int> first(nseg + 1, 0);
+  bool align8 = true;
   for (int k = 0; k < nseg; ++k) {
     first[k] = (int)ch.size();
     if (segs[k].offset < 0 || segs[k].numel < 0 || segs[k].offset + segs[k].numel > numel)
       return fa::set_err(FA_E_INVAL, "fa_norm_plan_create: segment %d outside bucket", k);
     if (segs[k].offset % 4)
       return fa::set_err(FA_E_ALIGN, "fa_norm_plan_create: segment %d not 16-B aligned", k);
+    if (segs[k].offset % 8) align8 = false;
     for (int64_t c = 0; c < segs[k].numel; c += kChunk)
       ch.push_back(NormChunk{segs[k].offset + c, (int32_t)std::min<int64_t>(kChunk, segs[k].numel - c), k});
   }
@@ -337,6 +343,7 @@ int fa_norm_plan_create(const fa_seg* segs, int nseg, int64_t numel, fa_norm_pla
   p->nseg = nseg;
   p->nchunks = (int)ch.size();
   p->numel = numel;
+  p->align8 = align8;
   hipError_t e = hipGetDevice(&p->device);
   if (e == hipSuccess && !ch.empty()) e = hipMalloc(&p->d_chunks, ch.size() * sizeof(NormChunk));
   if (e == hipSuccess) e = hipMalloc(&p->d_seg_first, first.size() * sizeof(int));
@@ -442,3 +449,29 @@ int fa_prox_grad_ex(const fa_norm_plan* p, const float* a, const float* b, const
 }
 
 }  // extern "C"
+
+// What prox_h16.hip needs of a plan (prox_plan.h).
+namespace fa_prox {
+
+PlanView view(const fa_norm_plan* p) {
+  return PlanView{p->nseg, p->nchunks, reinterpret_cast<const Chunk*>(p->d_chunks), p->d_seg_first,
+                  p->d_partials, p->align8};
+}
+
+size_t finish_lds_bytes(const fa_norm_plan* p) {
+  const size_t lds = (size_t)(p->nchunks + 2 * p->nseg + 1) * 4;
+  return lds <= kFinLdsMax ? lds : 0;
+}
+
+hipError_t launch_finish_f32(const fa_norm_plan* p, float* norms, float* total, hipStream_t st) {
+  const size_t lds = finish_lds_bytes(p);
+  if (lds)
+    hipLaunchKernelGGL(prox_finish<true>, dim3(1), dim3(kFinBlk), lds, st, p->d_seg_first,
+                       p->nseg, p->nchunks, p->d_partials, norms, total);
+  else
+    hipLaunchKernelGGL(prox_finish<false>, dim3(1), dim3(kFinBlk), 0, st, p->d_seg_first,
+                       p->nseg, p->nchunks, p->d_partials, norms, total);
+  return hipGetLastError();
+}
+
+}  // namespace fa_prox

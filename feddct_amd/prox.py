@@ -11,6 +11,12 @@ global_model)`` — the same value (to fp32 rounding) and the same gradients
 for BOTH models' parameters (the reference's graph also reaches the global
 model's parameters), computed by three HIP launches (two forward, one backward) over the two arenas
 (csrc/prox.hip) instead of 2·K norm/sub kernels plus their backward.
+
+A ``model.half()`` / ``model.bfloat16()`` client paired with a global of the
+same 16-bit dtype, or with an fp32 master global, runs natively too
+(csrc/prox_h16.hip), over the arenas ``server_aggregate`` binds for those
+models: the term and every gradient have the dtype and the 16-bit roundings
+torch gives the loop.
 """
 from __future__ import annotations
 
@@ -42,9 +48,20 @@ class _NormPlan:
                 pass
 
 
+SUPPORTED = ("supported pairs: an all-fp32 client and global; a client whose floating keys are "
+             "all fp16 or all bf16 with a global of the same dtype or an all-fp32 (master) "
+             "global — on one GPU, in the torch_cpu summation order")
+
+
 class _Prox(torch.autograd.Function):
     @staticmethod
     def forward(ctx, term, *params):
+        if term.h16 is not None:
+            norms = term.norms_buf()
+            total = term.norms16(norms)
+            ctx.term = term
+            ctx.save_for_backward(norms)
+            return total
         dev = term.ca.f32.device
         norms = torch.empty(max(1, term.plan.nseg), dtype=torch.float32, device=dev)
         total = torch.empty((), dtype=torch.float32, device=dev)
@@ -61,10 +78,16 @@ class _Prox(torch.autograd.Function):
         term = ctx.term
         (norms,) = ctx.saved_tensors
         dev = norms.device
-        gout = gout.to(dtype=torch.float32).contiguous()
         need_b = any(ctx.needs_input_grad[1 + len(term.slots):])
         ga = torch.empty_like(term.ca.f32)
         gb = torch.empty_like(term.ga.f32) if need_b else None
+        if term.h16 is not None:
+            term.grad16(norms, gout, ga, gb, 0)
+            grads_a = [ga[o:o + m].view(shape) for o, m, shape in term.slots]
+            grads_b = ([gb[o:o + m].view(shape) for o, m, shape in term.slots] if need_b
+                       else [None] * len(term.slots))
+            return (None, *grads_a, *grads_b)
+        gout = gout.to(dtype=torch.float32).contiguous()
         s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.lib.fa_prox_grad(term.plan.handle, term.ca.ptr32, term.ga.ptr32,
                                          norms.data_ptr(), gout.data_ptr(), 1.0,
@@ -106,11 +129,25 @@ class ProximalTerm:
 
     def __init__(self, client_model: torch.nn.Module, global_model: torch.nn.Module):
         from .aggregate import engine
-        layout = engine().layout_of(global_model)
         self.client_model, self.global_model = client_model, global_model
+        # a pair the 16-bit rounds reduce natively ("native": both 16-bit;
+        # "mixed": an fp32 master global) binds the arenas server_aggregate
+        # binds, so a FedProx loop never re-binds between a step and a round
+        kind, self.h16 = engine()._round_dtypes(global_model, [client_model])
+        if kind is None:
+            self.h16 = None
+            dts = {p.dtype for m in (client_model, global_model) for p in m.parameters()}
+            if dts - {torch.float32}:
+                raise NotImplementedError(
+                    "proximal term: parameters of dtypes "
+                    f"{sorted(str(d) for d in dts)} have no native form here; " + SUPPORTED)
+            layout = glayout = engine().layout_of(global_model)
+        else:
+            glayout, layout = engine().round_layouts(global_model, [client_model])
+        self.term_dtype = (torch.float32 if kind != "native" else self.h16)
         self.layout = layout
         self.ca = get_arena(client_model, layout)
-        self.ga = get_arena(global_model, layout)
+        self.ga = get_arena(global_model, glayout)
         if self.ca.device.type != "cuda":
             raise RuntimeError("feddct_amd.prox: models must be on the GPU (no CPU fallback)")
         cn = [n for n, _ in client_model.named_parameters()]
@@ -119,11 +156,16 @@ class ProximalTerm:
             raise RuntimeError("client and global models have different parameter counts")
         slots = []
         for a, b in zip(cn, gn):
-            sa, sb = layout.by_key.get(a), layout.by_key.get(b)
-            if sa is None or sb is None or sa.kind != "f32" or sb.offset != sa.offset:
+            sa, sb = layout.by_key.get(a), glayout.by_key.get(b)
+            ka = "f32" if self.h16 is None else "h16"
+            kb = "h16" if kind == "native" else "f32"
+            if (sa is None or sb is None or sa.kind != ka or sb.kind != kb
+                    or sb.offset != sa.offset or sb.numel != sa.numel):
                 raise NotImplementedError(
                     f"proximal term pairs parameters by position; {a!r} / {b!r} are not the "
-                    "same fp32 slot of one layout")
+                    "same fp32 slot of one layout" if self.h16 is None else
+                    f"proximal term pairs parameters by position; {a!r} / {b!r} are not at one "
+                    "element offset of the pair's 16-bit layouts; " + SUPPORTED)
             slots.append((sa.offset, sa.numel, sa.shape))
         self.slots = slots
         # the parameter objects are pinned by the arenas' validity checks:
@@ -133,6 +175,32 @@ class ProximalTerm:
         with torch.cuda.device(self.ca.device):
             self.plan = _NormPlan(segs, layout.f32_numel)
         self._flat = None   # gradient buckets of the one-node form, made on first use
+        if self.h16 is not None:
+            self.elem_a = _lib.ELEM_OF_DTYPE[self.h16]
+            self.elem_b = _lib.ELEM_OF_DTYPE[self.ga.f32.dtype]
+
+    # ------------------------------------------------ the 16-bit pairs --
+    def norms_buf(self) -> torch.Tensor:
+        """A fresh norms[] (fp32 storage; a 16-bit pair's hold 16-bit values)."""
+        return torch.empty(max(1, self.plan.nseg), dtype=torch.float32, device=self.ca.device)
+
+    def norms16(self, norms: torch.Tensor) -> torch.Tensor:
+        dev = self.ca.device
+        total = torch.empty((), dtype=self.term_dtype, device=dev)
+        s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib.fa_prox_norms_elem(
+            self.plan.handle, self.ca.ptr32, self.elem_a, self.ga.ptr32, self.elem_b,
+            norms.data_ptr(), total.data_ptr(), s), "fa_prox_norms_elem")
+        return total
+
+    def grad16(self, norms, gout, ga, gb, flags) -> None:
+        dev = self.ca.device
+        gout = gout.to(device=dev, dtype=self.term_dtype).contiguous()
+        s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib.fa_prox_grad_elem(
+            self.plan.handle, self.ca.ptr32, self.elem_a, self.ga.ptr32, self.elem_b,
+            norms.data_ptr(), gout.data_ptr(), 1.0, ga.data_ptr(),
+            None if gb is None else gb.data_ptr(), flags, s), "fa_prox_grad_elem")
 
     # ------------------------------------------------- the one-node form --
     def _flat_state(self):
@@ -174,6 +242,8 @@ class ProximalTerm:
 
     def norms_forward(self) -> torch.Tensor:
         _, _, norms = self._flat_state()
+        if self.h16 is not None:
+            return self.norms16(norms)
         dev = self.ca.device
         total = torch.empty((), dtype=torch.float32, device=dev)
         s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -188,7 +258,8 @@ class ProximalTerm:
         from . import _fa_shim
         sides, _, norms = self._flat_state()
         dev = self.ca.device
-        gout = gout.to(device=dev, dtype=torch.float32).contiguous()
+        if self.h16 is None:
+            gout = gout.to(device=dev, dtype=torch.float32).contiguous()
         states = []
         for params, views, buf in sides:
             if buf is None:
@@ -213,11 +284,15 @@ class ProximalTerm:
                  | (_lib.FA_PROX_ACCUMULATE_B if states[1] == 0 else 0))
         (_, _, ba), (_, _, bb) = sides
         s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib.fa_prox_grad_ex(
-            self.plan.handle, self.ca.ptr32, self.ga.ptr32, norms.data_ptr(), gout.data_ptr(),
-            1.0, ba.data_ptr() if ba is not None else self._scratch(dev).data_ptr(),
-            None if bb is None else bb.data_ptr(), flags, s),
-            "fa_prox_grad_ex")
+        if self.h16 is not None:
+            self.grad16(norms, gout, ba if ba is not None else self._scratch(dev), bb, flags)
+        else:
+            _lib.check(_lib.lib.fa_prox_grad_ex(
+                self.plan.handle, self.ca.ptr32, self.ga.ptr32, norms.data_ptr(),
+                gout.data_ptr(), 1.0,
+                ba.data_ptr() if ba is not None else self._scratch(dev).data_ptr(),
+                None if bb is None else bb.data_ptr(), flags, s),
+                "fa_prox_grad_ex")
         for (params, views, buf), st in zip(sides, states):
             if st == 1:
                 _fa_shim.bind_grads(params, views)
@@ -238,7 +313,8 @@ class ProximalTerm:
         if flat_grads:
             _, anchor, _ = self._flat_state()
             from . import _fa_shim
-            if hasattr(_fa_shim, "prox_apply"):
+            # (the C++ node is fp32-only: a 16-bit pair takes the Python node)
+            if self.h16 is None and hasattr(_fa_shim, "prox_apply"):
                 dev = self.ca.device
                 return _fa_shim.prox_apply(self._native(), anchor,
                                            torch.cuda.current_stream(dev).cuda_stream)
@@ -269,7 +345,21 @@ def proximal_term(client_model: torch.nn.Module, global_model: torch.nn.Module,
     see its share of ``.grad``, double backward raises, and with gradient
     accumulation the fp32 sum is (g + prox) + task rather than
     g + (task + prox) (equal to rounding).  Use it only where the step is
-    ``loss.backward()`` followed by the optimizer."""
+    ``loss.backward()`` followed by the optimizer.
+
+    fp16 / bf16 models (``model.half()`` / ``model.bfloat16()``): a client
+    whose floating keys all have one 16-bit dtype, paired with a global of
+    that dtype or with an all-fp32 master global, on one GPU in the torch_cpu
+    order, runs natively on the arenas ``server_aggregate`` binds for them.
+    The term is a 0-dim tensor of the dtype torch gives the loop (the 16-bit
+    dtype, or fp32 over a master global), each gradient has its parameter's
+    dtype, and every 16-bit rounding is torch's CPU one (the in-order 16-bit
+    running sum of the 16-bit norms included).  ``flat_grads=True`` works
+    for these pairs through the Python one-node form, with a gradient bucket
+    in each side's dtype; the C++ node is fp32-only and is not used for them.
+    Every other pair raises ``NotImplementedError``: a 16-bit global over
+    fp32 clients, mixed dtypes inside one model, the ``torch_gpu`` order,
+    host-resident 16-bit models."""
     cache = client_model.__dict__.setdefault("_fa_prox", {})
     t = cache.get(id(global_model))
     if t is None or t.global_model is not global_model or not t.valid():

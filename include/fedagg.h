@@ -398,6 +398,32 @@ int fa_prox_grad(const fa_norm_plan *plan, const float *a, const float *b,
 int fa_prox_grad_ex(const fa_norm_plan *plan, const float *a, const float *b,
                     const float *norms, const float *gout, float alpha,
                     float *grad_a, float *grad_b, unsigned flags, void *stream);
+/* The same for buckets of other element types (FA_ELEM_*): a in a_elem
+ * elements (the client's), b in b_elem elements (the global's), at the same
+ * ELEMENT offsets.  Accepted (a_elem, b_elem):
+ *   (F32, F32)                 fa_prox_norms / fa_prox_grad_ex exactly;
+ *   (F16, F16), (BF16, BF16)   the term of a model.half() / model.bfloat16()
+ *     pair as torch computes it: d = rn16(a - b); norms[k] (fp32 storage) =
+ *     rn16(sqrt(sum d^2)), the squares summed in fp32; *total (16-bit) the
+ *     running 16-bit sum of the norms in segment order; *gout 16-bit;
+ *     grad_a = rn16(rn16(gout * alpha) * rn16(d / norms[k])), 0 where
+ *     norms[k] == 0, grad_b = -grad_a, both 16-bit; an accumulating side is
+ *     rn16(old + new);
+ *   (F16, F32), (BF16, F32)    an fp32 master global: a - b promotes to fp32,
+ *     so norms, *total, *gout and grad_b are the fp32 entry points' on the
+ *     widened a, and grad_a = rn16 of the fp32 gradient (accumulating:
+ *     rn16(old + that)).
+ * Every other pair is FA_E_INVAL.  With a 16-bit a every segment offset of
+ * the plan must be a multiple of 8 elements and every bucket 16-B aligned
+ * (FA_E_ALIGN).  A refused call launches nothing.  fa_tune_prox_* do not
+ * reach the 16-bit kernels. */
+int fa_prox_norms_elem(const fa_norm_plan *plan, const void *a, int a_elem,
+                       const void *b, int b_elem, float *norms, void *total,
+                       void *stream);
+int fa_prox_grad_elem(const fa_norm_plan *plan, const void *a, int a_elem,
+                      const void *b, int b_elem, const float *norms,
+                      const void *gout, float alpha, void *grad_a, void *grad_b,
+                      unsigned flags, void *stream);
 
 /* Streaming copy (bandwidth ceiling calibration for the roofline). */
 int fa_copy_f32(const float *src, float *dst, int64_t numel, void *stream);
