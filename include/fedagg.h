@@ -265,8 +265,10 @@ int fa_plan_launch_form(const fa_plan *plan, int n, int weighted, int *tile_elem
  *   float(M)/float(N*M); M == 1 keys: lane split + the intra-wave shuffle
  *   tree.  The cut depends on N, so the plan is made for one client count;
  *   unweighted only.  fa_torch_gpu_config() says whether (N, M) is inside
- *   the restated configurations (no cross-block split: ceil(N/S) < 256,
- *   S <= 16; M == 1 needs N < 128) and gives S. */
+ *   the restated configurations (N >= 2; M > 1: S <= 16 and no cross-block
+ *   split, which torch makes only once ceil(N/S) >= 256 on a small output
+ *   grid; M == 1: every N up to FA_MAX_CLIENTS, the input-vectorised lane
+ *   form from N >= 128 on) and gives S (M == 1: the block width). */
 #define FA_ORDER_TORCH_CPU 0
 #define FA_ORDER_TORCH_GPU 1
 int fa_torch_gpu_config(int n, int64_t m, int *stride);
@@ -277,7 +279,9 @@ int fa_plan_create_order(const fa_seg *seg32, int nseg32, int64_t f32_numel,
 /* The hot path: every key of N client buckets -> global bucket, one launch
  * (FA_F_BCAST: plus one broadcast launch — over the same tiles, or the flat
  * bucket copy when the plan covers the whole bucket, see FA_F_BCAST).
- *   c32[i] / c64[i]  : client i's fp32 / int64 bucket (slot order 0..n-1)
+ *   c32[i] / c64[i]  : client i's fp32 / int64 bucket (slot order 0..n-1); a
+ *                      bucket may appear more than once (clients sampled
+ *                      with replacement): its rows count once per slot
  *   weights          : NULL -> mean (sum / n);  else fp32 w[i], result =
  *                      ordered sum of fp32(x_i * w_i) (no division)
  *   out32 / out64    : global buckets (may alias a client bucket)
