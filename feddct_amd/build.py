@@ -33,7 +33,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 # public ABI, so the core library does not depend on RCCL.  librccl.so.1
 # resolves to the copy torch has already loaded (same soname).
 COMM_SRC = os.path.join(HERE, "csrc", "fedcomm.hip")
-COMM_DEPS = [COMM_SRC, os.path.join(HERE, "csrc", "common.h"), os.path.join(HERE, "csrc", "err.h"),
+# the schedules and the cost model: host code only, compiled as plain C++
+COMM_HOST_SRC = os.path.join(HERE, "csrc", "sched_host.cpp")
+COMM_DEPS = [COMM_SRC, COMM_HOST_SRC, os.path.join(HERE, "csrc", "sched_host.h"),
+             os.path.join(HERE, "csrc", "common.h"), os.path.join(HERE, "csrc", "err.h"),
              os.path.join(HERE, "..", "include", "fedagg.h"),
              os.path.join(HERE, "..", "include", "fedagg_comm.h")]
 COMM_OUT = os.path.join(HERE, "libfedagg_comm.so")
@@ -76,21 +79,22 @@ def _stale(out, deps):
                                                                    for d in deps)
 
 
-def _compile_units(srcs, flags, jobs=None, force=False):
+def _compile_units(srcs, flags, jobs=None, force=False, headers=HEADERS):
     """hipcc -c of every stale unit (older than its source or a shared
     header), several at once; returns the object paths."""
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     jobs = jobs or min(len(srcs), int(os.environ.get("MAX_JOBS", "0")) or os.cpu_count() or 4, 16)
     cflags = [f for f in flags if f not in ("-shared",)]
-    # a .cpp unit holds no device code (plan_host.cpp: the planners): plain
-    # C++, no offload arch; -D overrides reach it like every other unit
+    # a .cpp unit holds no device code (plan_host.cpp: the planners;
+    # sched_host.cpp: the multi-GPU schedules): plain C++, no offload arch;
+    # -D overrides reach it like every other unit
     host = ["-x", "c++"] + [f for f in cflags if not f.startswith("--offload-arch")]
     objs, procs = [], []
     for src in srcs:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
-        if not force and not _stale(obj, [src] + HEADERS):
+        if not force and not _stale(obj, [src] + headers):
             continue
         while len([p for p in procs if p.poll() is None]) >= jobs:
             procs[[p.poll() is None for p in procs].index(True)].wait()
@@ -102,6 +106,13 @@ def _compile_units(srcs, flags, jobs=None, force=False):
     return objs
 
 
+def _comm_objs(force, extra):
+    """The objects of fedcomm.hip and sched_host.cpp: libfedagg_comm.so and
+    its loopback copy link the same two."""
+    return _compile_units([COMM_SRC, COMM_HOST_SRC], [*FLAGS, *extra],
+                          force=force or bool(extra), headers=COMM_DEPS)
+
+
 def build(force: bool = False, extra=()) -> str:
     if force or _stale(OUT, DEPS):
         objs = _compile_units(SRCS, [*FLAGS, *extra], force=force or bool(extra))
@@ -109,7 +120,8 @@ def build(force: bool = False, extra=()) -> str:
         subprocess.run(cmd, check=True)
         os.replace(OUT + ".tmp", OUT)
     if force or _stale(COMM_OUT, COMM_DEPS + [OUT]):
-        cmd = [HIPCC, *FLAGS, *extra, "-o", COMM_OUT + ".tmp", COMM_SRC, "-L" + HERE, "-lfedagg",
+        cmd = [HIPCC, *FLAGS, *extra, "-o", COMM_OUT + ".tmp", *_comm_objs(force, extra),
+               "-L" + HERE, "-lfedagg",
                "-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,$ORIGIN"]
         subprocess.run(cmd, check=True)
         os.replace(COMM_OUT + ".tmp", COMM_OUT)
@@ -158,7 +170,8 @@ def build_loopback(force: bool = False, extra=()) -> str:
         os.replace(ccl + ".tmp", ccl)
     if force or _stale(comm, COMM_DEPS + [OUT, ccl]):
         subprocess.run([HIPCC, *FLAGS, *extra, "-Wl,-soname,libfedagg_comm_loop.so", "-o", comm + ".tmp",
-                        COMM_SRC, "-L" + HERE, "-lfedagg", "-L" + LOOP_DIR, "-lloopccl",
+                        *_comm_objs(False, extra), "-L" + HERE, "-lfedagg",
+                        "-L" + LOOP_DIR, "-lloopccl",
                         "-Wl,-rpath,$ORIGIN:$ORIGIN/../../feddct_amd"], check=True)
         os.replace(comm + ".tmp", comm)
     if force or _stale(drv, [drv_src, comm, os.path.join(HERE, "..", "include", "fedagg_comm.h")]):

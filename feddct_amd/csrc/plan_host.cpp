@@ -805,3 +805,87 @@ Launch select_launch(const PlanShape& plan, int n, bool weighted, SlotFn slots) 
 }
 
 }  // namespace fa_host
+
+// ---- host-only C ABI (fedagg.h); sched_host.cpp calls the first and last --
+using fa::set_err;
+using namespace fa_k;
+
+namespace {
+// One body behind fa_plan_build_host and fa_plan_build_host_elem.
+int plan_build_host(const char* who, const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                    const fa_seg* seg64, int nseg64, int64_t i64_numel, int tile_elems,
+                    unsigned flags, int elem, fa_tile_desc* tiles, int cap, fa_plan_info* info) {
+  if (!info) return set_err(FA_E_INVAL, "%s: info is NULL", who);
+  fa_host::Layout l;
+  int rc = fa_host::parse_layout(who, "", fa_host::kCheckTile, seg32, nseg32, f32_numel, seg64,
+                                 nseg64, i64_numel, tile_elems, flags, elem, &l);
+  if (rc) return rc;
+  std::vector<Tile> t;
+  rc = fa_host::build_tiles(l.s32, l.s64, l.info.tile_elems, flags, &t, &l.info, l.valign);
+  if (rc) return rc;
+  *info = l.info;
+  if (tiles) {
+    if (cap < (int)t.size())
+      return set_err(FA_E_RANGE, "%s: %d tiles, capacity %d", who, (int)t.size(), cap);
+    for (size_t i = 0; i < t.size(); ++i) tiles[i] = fa_tile_desc{t[i].start, t[i].count, t[i].kind};
+  }
+  return FA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fa_plan_build_host(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
+                       int nseg64, int64_t i64_numel, int tile_elems, unsigned flags,
+                       fa_tile_desc* tiles, int cap, fa_plan_info* info) {
+  return plan_build_host("fa_plan_build_host", seg32, nseg32, f32_numel, seg64, nseg64, i64_numel,
+                         tile_elems, flags, FA_ELEM_F32, tiles, cap, info);
+}
+
+int fa_plan_build_host_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                            const fa_seg* seg64, int nseg64, int64_t i64_numel, int tile_elems,
+                            unsigned flags, int elem, fa_tile_desc* tiles, int cap,
+                            fa_plan_info* info) {
+  if (elem == FA_ELEM_F32)
+    return fa_plan_build_host(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems,
+                              flags, tiles, cap, info);
+  return plan_build_host("fa_plan_build_host_elem", seg32, nseg32, f32_numel, seg64, nseg64,
+                         i64_numel, tile_elems, flags, elem, tiles, cap, info);
+}
+
+int fa_plan_balance_host(const fa_tile_desc* vec, int nvec, int tile_elems, int nscalar,
+                         int slots, fa_tile_desc* out, int cap) {
+  if (nvec < 0 || (nvec > 0 && !vec) || nscalar < 0 || slots < 0 || cap < 0 ||
+      (cap > 0 && !out))
+    return set_err(FA_E_INVAL, "fa_plan_balance_host: bad arguments");
+  if (tile_elems != 4 * kBlock && tile_elems != 8 * kBlock && tile_elems != 16 * kBlock)
+    return set_err(FA_E_INVAL, "tile_elems must be 1024, 2048 or 4096 (got %d)", tile_elems);
+  std::vector<Tile> t;
+  for (int i = 0; i < nvec; ++i) {
+    if (vec[i].kind != K_F32_VEC || vec[i].count < 4 || vec[i].count % 4 ||
+        vec[i].count > tile_elems || vec[i].start % 4)
+      return set_err(FA_E_INVAL, "fa_plan_balance_host: tile %d is not a vector tile", i);
+    t.push_back(Tile{vec[i].start, vec[i].count, vec[i].kind});
+  }
+  const std::vector<Tile> b = fa_host::balance_vec(t, tile_elems, nscalar, slots);
+  if ((int64_t)b.size() > (int64_t)cap)
+    return set_err(FA_E_RANGE, "fa_plan_balance_host: %zu tiles > cap %d", b.size(), cap);
+  for (size_t i = 0; i < b.size(); ++i) out[i] = fa_tile_desc{b[i].start, b[i].count, b[i].kind};
+  return (int)b.size();
+}
+
+unsigned fa_chain_levels(int rows, int n_total) {
+  if (rows <= 0 || n_total < 1) return 0;
+  const int lp = level_power(n_total);
+  const int step = 1 << lp;
+  unsigned m = 0;
+  if (rows % step) m |= 1u;                     // the open block
+  if ((rows >> lp) % step) m |= 2u;             // completed blocks since the last promotion
+  if (n_total >= 256) {                         // levels 2-3 exist (DEEP kernels)
+    if ((rows >> (2 * lp)) % step) m |= 4u;
+    if (rows >> (3 * lp)) m |= 8u;              // level 3 only accumulates
+  }
+  return m;
+}
+
+}  // extern "C"

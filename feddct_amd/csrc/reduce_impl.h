@@ -132,19 +132,6 @@ __device__ __forceinline__ void load_weights(KArgs& a, int b0, int nb, float (&w
   }
 }
 
-// c10::utils::CeilLog2 / ATen multi_row_sum level power
-__host__ __device__ inline int ceil_log2_i(int64_t n) {
-  if (n <= 1) return 0;
-  int r = 0;
-  uint64_t v = (uint64_t)(n - 1);
-  while (v) { ++r; v >>= 1; }
-  return r;
-}
-__host__ __device__ inline int level_power(int64_t n) {
-  int c = ceil_log2_i(n) / 4;
-  return c > 4 ? c : 4;
-}
-
 __device__ __forceinline__ f4 add4(f4 a, f4 b) {
   return f4{__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z),
             __fadd_rn(a.w, b.w)};

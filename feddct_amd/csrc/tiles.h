@@ -61,6 +61,20 @@ constexpr int64_t kTorchMaxThreadsPerCU = 2048;  // float4 vectors per thread pe
 // tile_scalar_packed): one per lane of wave 0.
 constexpr int kPackCols = 64;
 
+// c10::utils::CeilLog2 / ATen multi_row_sum level power: the cascade's level
+// step for n rows, read by the kernels and by the host's chain levels alike
+FA_HOST_DEVICE inline int ceil_log2_i(int64_t n) {
+  if (n <= 1) return 0;
+  int r = 0;
+  uint64_t v = (uint64_t)(n - 1);
+  while (v) { ++r; v >>= 1; }
+  return r;
+}
+FA_HOST_DEVICE inline int level_power(int64_t n) {
+  int c = ceil_log2_i(n) / 4;
+  return c > 4 ? c : 4;
+}
+
 }  // namespace fa_k
 
 namespace fa_h16 {

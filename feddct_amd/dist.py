@@ -67,7 +67,7 @@ def cascade_lp(n: int) -> int:
 
 
 def blocked_allowed(counts: Sequence[int]) -> bool:
-    """The blocked round's precondition (fedcomm.hip first_wide_block): every
+    """The blocked round's precondition (sched_host.cpp first_wide_block): every
     cascade block of 2**lp slots lies on at most two of the ranks holding
     slots."""
     first, n = [], 0
@@ -86,7 +86,7 @@ def blocked_allowed(counts: Sequence[int]) -> bool:
 def exact_form(counts: Sequence[int], layout: Optional[BucketLayout] = None,
                root_all: bool = False) -> str:
     """The exact round the default entry takes for these shard counts: the
-    form with the lowest modelled time (fedcomm.hip fa_multi_select_layout
+    form with the lowest modelled time (sched_host.cpp fa_multi_select_layout
     on ``layout``; None: fa_multi_select's nominal layout) — "blocked" (only
     where ``blocked_allowed``), "chained" or "striped".  ``root_all``: the
     result goes to every rank.  r05: "blocked" if allowed, else "chained"."""
@@ -95,7 +95,7 @@ def exact_form(counts: Sequence[int], layout: Optional[BucketLayout] = None,
 
 
 def stripe_schedule(bounds, shards, me, root=-1):
-    """The striped round's exchange steps for rank ``me`` (fedcomm.hip
+    """The striped round's exchange steps for rank ``me`` (sched_host.cpp
     sched_striped, its steps 2..C+3): per step, in issue order,
     ("send", peer, slot, offset, count) / ("recv", peer, slot, offset, count)
     for client rows, ("send_out", peer, offset, count) / ("recv_out", peer,

@@ -37,7 +37,7 @@ def cut_index(t: np.ndarray, parts: int, fractions=None) -> List[int]:
     """Group boundaries (tile indices, len parts+1) of the sorted tiles ``t``
     into ``parts`` runs of about equal element count (or of the given
     ``fractions`` of it, which sum to 1), cut only before a vector tile on a
-    256-B boundary — fedcomm.hip's cut_tiles, the same rule the native
+    256-B boundary — sched_host.cpp's cut_tiles, the same rule the native
     schedules use."""
     total = int(t[:, 1].sum()) if len(t) else 0
     if fractions is None:
@@ -80,7 +80,7 @@ def split_tiles(tiles: np.ndarray, parts: int, f32_numel: int, fractions=None
 
 
 def stripe_chunks(tiles: np.ndarray, parts: int, f32_numel: int, nchunks: int):
-    """The striped round's cut (fedcomm.hip build_round, r06): ``parts``
+    """The striped round's cut (sched_host.cpp build_round, r06): ``parts``
     stripes (split_tiles), each cut into ``nchunks`` column chunks by the
     same rule.  Returns, per stripe, [(lo, hi, tiles)] of its chunks, in
     order, covering the stripe exactly (trailing chunks may be empty)."""
@@ -116,7 +116,7 @@ def range_plans(layout: BucketLayout, parts: int, tile_elems: int = 0, flags=Non
 
 
 def chain_cut(layout: BucketLayout, nchunks: int):
-    """The chained round's cut (fedcomm.hip chain_geo): the vector (cascade)
+    """The chained round's cut (sched_host.cpp chain_geo): the vector (cascade)
     tiles in ``nchunks`` column chunks [(lo, hi, tiles)], empty ones dropped;
     the scalar fp32 tiles re-based to compact columns (tiles, and the bucket
     index of each compact column); the int64 tiles."""

@@ -1,6 +1,9 @@
 """The round cost model restated in Python (test infrastructure; r06).
 
-fedcomm.hip's fa_round_model times every rank's schedule (fa_describe_round)
+fa_round_model (feddct_amd/csrc/sched_host.cpp, the HIP-free host unit of
+libfedagg_comm.so: model_schedules, kernel_bytes, coll_link_bytes and the
+stream-rule predicates the executor in fedcomm.hip shares) times every rank's
+schedule (fa_describe_round)
 in virtual time under the executor's stream rules; this module replays the
 same schedules (``feddct_amd.comm.describe``) by the rules written out again
 from the header (include/fedagg_comm.h, "the round cost model"), so a test

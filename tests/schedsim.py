@@ -18,7 +18,7 @@ RCCL or a GPU.  Only the arithmetic of the kernels is substituted, and that
 is pinned by the GPU tests.
 
 r06: the executor's stream rules are checked too.  A compute-stream kernel
-that reads exchanged data (the striped round's chunk reduce, fedcomm.hip
+that reads exchanged data (the striped round's chunk reduce, sched_host.cpp
 reads_exchanged) runs concurrently with its own step's group: it must not
 read what that group receives, nor write what that group sends or receives;
 and a step's sends must not read what the same step's kernels write (they

@@ -1,6 +1,7 @@
 """The native multi-GPU schedules (libfedagg_comm.so), all ranks at once, on
-a CPU: fa_describe_round gives each rank's exact
-list of exchanges and kernels; tests/schedsim.py replays the lists of every
+a CPU: fa_describe_round (the schedule builders of
+feddct_amd/csrc/sched_host.cpp, the library's HIP-free host unit) gives each
+rank's exact list of exchanges and kernels; tests/schedsim.py replays the lists of every
 rank together under RCCL's group/matching rules with the oracle as the
 arithmetic.  Covers world sizes 2-8, uneven and empty shards, every root,
 weighted rounds, and both e1 exchanges:
