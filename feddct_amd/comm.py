@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dist import shard_range
+from .dist import check_final, shard_counts
 from .layout import BucketLayout
 
 COMM_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfedagg_comm.so")
@@ -177,15 +177,13 @@ def multi_select(counts: Sequence[int], exact: bool = True, layout: Optional[Buc
     ``layout`` (None: fa_multi_select's nominal 2^24-float layout).
     ``root_all``: the result on every rank (FA_MULTI_ROOT_ALL) rather than on
     the last rank holding slots.  ``detail``: (form, nchunks, model_us)."""
-    c = (_I * len(counts))(*map(int, counts))
+    c = _counts(counts)
     m, k, us = _I(), _I(), ctypes.c_double()
     if layout is None:
         _lib.check(lib().fa_multi_select(len(counts), c, _mflags(exact, root_all),
                                          ctypes.byref(m)), "fa_multi_select")
         return (MODE_NAMES[m.value], None, None) if detail else MODE_NAMES[m.value]
-    a32, n32, a64, n64 = _segs(layout)
-    _lib.check(lib().fa_multi_select_layout(len(counts), c, a32, n32, int(layout.f32_numel), a64,
-                                            n64, int(layout.i64_numel),
+    _lib.check(lib().fa_multi_select_layout(len(counts), c, *_layout_args(layout),
                                             _lib.FA_PLAN_GAPS_ARE_PADDING,
                                             _mflags(exact, root_all), ctypes.byref(m),
                                             ctypes.byref(k), ctypes.byref(us)),
@@ -209,11 +207,9 @@ def round_model(mode: int, layout: BucketLayout, counts: Sequence[int], nchunks:
     """The cost model's view of one round (fa_round_model, host only): the
     modelled time in microseconds, the largest byte count on one link
     direction, the largest per-rank HBM byte count, group and step counts."""
-    a32, n32, a64, n64 = _segs(layout)
-    c = (_I * len(counts))(*map(int, counts))
     out = FaRoundCost()
-    _lib.check(lib().fa_round_model(int(mode), len(counts), c, a32, n32, int(layout.f32_numel),
-                                    a64, n64, int(layout.i64_numel), int(nchunks), int(exchange),
+    _lib.check(lib().fa_round_model(int(mode), len(counts), _counts(counts),
+                                    *_layout_args(layout), int(nchunks), int(exchange),
                                     _lib.FA_PLAN_GAPS_ARE_PADDING, int(root), int(bool(weighted)),
                                     ctypes.byref(out)), "fa_round_model")
     return {f: getattr(out, f) for f, _ in FaRoundCost._fields_}
@@ -225,10 +221,17 @@ def unique_id() -> bytes:
     return buf.raw
 
 
-def _segs(layout: BucketLayout):
+def _layout_args(layout: BucketLayout):
+    """A layout as the C ABI takes it: seg32, nseg32, f32_numel, seg64,
+    nseg64, i64_numel."""
     a32, n32 = _lib.seg_array(layout.segs32 if len(layout.segs32) else np.zeros((0, 2), np.int64))
     a64, n64 = _lib.seg_array(layout.segs64 if len(layout.segs64) else np.zeros((0, 2), np.int64))
-    return a32, n32, a64, n64
+    return a32, n32, int(layout.f32_numel), a64, n64, int(layout.i64_numel)
+
+
+def _counts(counts: Sequence[int]):
+    """Slots per rank as the C ABI takes them (an int array)."""
+    return (_I * len(counts))(*map(int, counts))
 
 
 def describe(mode: int, layout: BucketLayout, counts: Sequence[int], rank: int,
@@ -237,12 +240,9 @@ def describe(mode: int, layout: BucketLayout, counts: Sequence[int], rank: int,
     """Rank ``rank``'s schedule of one round (fa_describe_round): the exact
     list of exchanges and kernels the native executor issues, computed on the
     host (no GPU, no communicator)."""
-    a32, n32, a64, n64 = _segs(layout)
-    c = (_I * len(counts))(*map(int, counts))
     n = _I()
-    args = (mode, len(counts), rank, c, a32, n32, int(layout.f32_numel), a64, n64,
-            int(layout.i64_numel), int(nchunks), int(exchange), _lib.FA_PLAN_GAPS_ARE_PADDING,
-            int(root), int(bool(weighted)))
+    args = (mode, len(counts), rank, _counts(counts), *_layout_args(layout), int(nchunks),
+            int(exchange), _lib.FA_PLAN_GAPS_ARE_PADDING, int(root), int(bool(weighted)))
     _lib.check(lib().fa_describe_round(*args, None, 0, ctypes.byref(n)), "fa_describe_round")
     arr = (FaXfer * max(1, n.value))()
     _lib.check(lib().fa_describe_round(*args, arr, n.value, ctypes.byref(n)), "fa_describe_round")
@@ -332,29 +332,93 @@ def plan_profile(plan) -> dict:
                 else getattr(out, f)) for f, _ in FaRoundProfile._fields_}
 
 
-class ShardPlan:
-    """This rank's shard plan for a layout (chunk subplans + scratch)."""
+class _Plan:
+    """What the plan classes share: ``handle``, and ``comm`` (the plan must
+    not outlive its communicator).  A subclass names its create entry point,
+    the label its failure carries in FedaggError's text, and its destroy
+    entry point; ``extra`` are the create call's arguments between the counts
+    and the out-handle."""
+    _create = _label = _destroy = None
 
-    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int],
-                 nchunks: int = 8, exchange: int = FA_XCHG_REDUCE):
-        a32, n32, a64, n64 = _segs(layout)
-        c = (_I * len(counts))(*map(int, counts))
+    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int], *extra):
         h = _P()
-        _lib.check(lib().fa_shard_plan_create_ex(comm.handle, a32, n32, int(layout.f32_numel),
-                                                 a64, n64, int(layout.i64_numel), c, int(nchunks),
-                                                 int(exchange), _lib.FA_PLAN_GAPS_ARE_PADDING,
-                                                 ctypes.byref(h)), "fa_shard_plan_create")
+        _lib.check(getattr(lib(), self._create)(comm.handle, *_layout_args(layout),
+                                                _counts(counts), *extra, ctypes.byref(h)),
+                   self._label)
         self.handle = h
-        self.comm = comm  # the plan must not outlive its communicator
+        self.comm = comm
 
     def __del__(self):
         h = getattr(self, "handle", None)
         if h is not None and h.value:
             try:
-                lib().fa_shard_plan_destroy(h)
+                getattr(lib(), self._destroy)(h)
             except Exception:
                 pass
             self.handle = None
+
+
+class ShardPlan(_Plan):
+    """This rank's shard plan for a layout (chunk subplans + scratch)."""
+    _create, _label = "fa_shard_plan_create_ex", "fa_shard_plan_create"
+    _destroy = "fa_shard_plan_destroy"
+
+    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int],
+                 nchunks: int = 8, exchange: int = FA_XCHG_REDUCE):
+        super().__init__(comm, layout, counts, int(nchunks), int(exchange),
+                         _lib.FA_PLAN_GAPS_ARE_PADDING)
+
+
+class StripePlan(_Plan):
+    """This rank's exact-mode plan for a layout (its stripe's chunk plans, the
+    receive rows, int64 gather buffers; nchunks 0 = 4)."""
+    _create, _label = "fa_stripe_plan_create_ex", "fa_stripe_plan_create"
+    _destroy = "fa_stripe_plan_destroy"
+
+    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int],
+                 nchunks: int = 0):
+        super().__init__(comm, layout, counts, int(nchunks), _lib.FA_PLAN_GAPS_ARE_PADDING)
+
+
+class ChainPlan(_Plan):
+    """This rank's chained-mode plan (vector-tile chunk plans, the state
+    planes, the raw scalar-column gather buffers)."""
+    _create = _label = "fa_chain_plan_create"
+    _destroy = "fa_chain_plan_destroy"
+
+    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int],
+                 nchunks: int = 16):
+        super().__init__(comm, layout, counts, int(nchunks), _lib.FA_PLAN_GAPS_ARE_PADDING)
+
+
+class BlockPlan(_Plan):
+    """This rank's blocked-mode plan (block-sum planes, the stripe it owns,
+    relay rows, the raw scalar-column gather buffers)."""
+    _create = _label = "fa_block_plan_create"
+    _destroy = "fa_block_plan_destroy"
+
+    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int]):
+        super().__init__(comm, layout, counts, _lib.FA_PLAN_GAPS_ARE_PADDING)
+
+
+class MultiPlan(_Plan):
+    """This rank's plan of the default round (fa_multi_plan_create): the form
+    and chunk count the cost model picks for ``counts`` on ``layout``
+    (``mode``, ``nchunks`` name them); ``root_all``: the model's root is
+    every rank (FA_MULTI_ROOT_ALL)."""
+    _create = _label = "fa_multi_plan_create"
+    _destroy = "fa_multi_plan_destroy"
+
+    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int],
+                 nchunks: int = 0, exact: bool = True, root_all: bool = False):
+        super().__init__(comm, layout, counts, int(nchunks), _lib.FA_PLAN_GAPS_ARE_PADDING,
+                         _mflags(exact, root_all))
+        m, k = _I(), _I()
+        _lib.check(lib().fa_multi_plan_mode(self.handle, ctypes.byref(m)), "fa_multi_plan_mode")
+        _lib.check(lib().fa_multi_plan_chunks(self.handle, ctypes.byref(k)),
+                   "fa_multi_plan_chunks")
+        self.mode = MODE_NAMES[m.value]
+        self.nchunks = k.value
 
 
 class NativeShardedAggregator:
@@ -366,19 +430,36 @@ class NativeShardedAggregator:
 
     ``final="reduce"``: the global state lands on ``root`` (out buffers of the
     other ranks are untouched); ``"allreduce"``: on every rank."""
+    _entry = "fa_reduce_sharded"    # what step() calls, and its label
 
     def __init__(self, layout: BucketLayout, local32: List[torch.Tensor],
                  local64: List[torch.Tensor], n_total: int, out32: torch.Tensor,
                  out64: torch.Tensor, comm: Comm, nchunks: int = 8, final: str = "reduce",
                  root: int = 0, weights: Optional[Sequence[float]] = None,
                  exchange: int = FA_XCHG_REDUCE):
-        if final not in ("reduce", "allreduce"):
-            raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
+        self._bind(ShardPlan, (nchunks, exchange), layout, local32, local64, n_total, out32,
+                   out64, comm, final, root, weights)
+
+    def _bind(self, plan, plan_args, layout, local32, local64, n_total, out32, out64, comm,
+              final, root, weights, counts=None, world_counts=False):
+        """Every native aggregator's constructor: the checks, the plan
+        (``plan(comm, layout, counts, *plan_args)``) and the FaShardIO of the
+        round.  ``counts`` None: ``shard_counts``; ``root`` None: the last
+        rank holding slots.  ``world_counts``: len(counts) must be the world
+        size (NativeAggregator alone asks; the other forms take any counts
+        that name this rank's shard and sum to ``n_total``)."""
+        check_final(final)
         world, rank, _ = comm.info()
-        counts = [b - a for a, b in (shard_range(n_total, world, r) for r in range(world))]
-        if len(local32) != counts[rank]:
-            raise ValueError(f"rank {rank} holds {len(local32)} clients, shard is {counts[rank]}")
-        self.plan = ShardPlan(comm, layout, counts, nchunks, exchange)
+        if counts is None:
+            counts = shard_counts(n_total, world)
+        named = rank < len(counts)
+        if (not named or len(local32) != counts[rank] or sum(counts) != n_total
+                or (world_counts and len(counts) != world)):
+            raise ValueError(f"rank {rank} holds {len(local32)} clients, shard is "
+                             f"{counts[rank] if named else '?'}")
+        self.plan = plan(comm, layout, counts, *plan_args)
+        if root is None:
+            root = max(r for r in range(world) if counts[r] > 0)
         self.root = root if final == "reduce" else -1
         self._a32 = _lib.ptr_array([t.data_ptr() for t in local32])
         self._a64 = _lib.ptr_array([t.data_ptr() for t in local64])
@@ -396,34 +477,8 @@ class NativeShardedAggregator:
     def step(self, stream=None) -> None:
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         self.io.stream = s
-        _lib.check(lib().fa_reduce_sharded(self._plans, 1, ctypes.byref(self.io), self.root),
-                   "fa_reduce_sharded")
-
-
-class StripePlan:
-    """This rank's exact-mode plan for a layout (its stripe's chunk plans, the
-    receive rows, int64 gather buffers; nchunks 0 = 4)."""
-
-    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int],
-                 nchunks: int = 0):
-        a32, n32, a64, n64 = _segs(layout)
-        c = (_I * len(counts))(*map(int, counts))
-        h = _P()
-        _lib.check(lib().fa_stripe_plan_create_ex(comm.handle, a32, n32, int(layout.f32_numel),
-                                                  a64, n64, int(layout.i64_numel), c,
-                                                  int(nchunks), _lib.FA_PLAN_GAPS_ARE_PADDING,
-                                                  ctypes.byref(h)), "fa_stripe_plan_create")
-        self.handle = h
-        self.comm = comm
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None and h.value:
-            try:
-                lib().fa_stripe_plan_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
+        _lib.check(getattr(lib(), self._entry)(self._plans, 1, ctypes.byref(self.io), self.root),
+                   self._entry)
 
 
 class NativeStripedAggregator(NativeShardedAggregator):
@@ -432,65 +487,15 @@ class NativeStripedAggregator(NativeShardedAggregator):
     result is bit-identical to one GPU reducing all clients.  r06: every
     peer in one RCCL group per column chunk (``nchunks``, 0 = 4), weighted
     rounds too (``weights``: this rank's fp32 client weights)."""
+    _entry = "fa_reduce_striped"
 
     def __init__(self, layout: BucketLayout, local32: List[torch.Tensor],
                  local64: List[torch.Tensor], n_total: int, out32: torch.Tensor,
                  out64: torch.Tensor, comm: Comm, final: str = "reduce", root: int = 0,
                  weights: Optional[Sequence[float]] = None,
                  counts: Optional[Sequence[int]] = None, nchunks: int = 0):
-        if final not in ("reduce", "allreduce"):
-            raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
-        world, rank, _ = comm.info()
-        if counts is None:
-            counts = [b - a for a, b in (shard_range(n_total, world, r) for r in range(world))]
-        if len(local32) != counts[rank] or sum(counts) != n_total:
-            raise ValueError(f"rank {rank} holds {len(local32)} clients, shard is {counts[rank]}")
-        self.plan = StripePlan(comm, layout, counts, nchunks)
-        self.root = root if final == "reduce" else -1
-        self._a32 = _lib.ptr_array([t.data_ptr() for t in local32])
-        self._a64 = _lib.ptr_array([t.data_ptr() for t in local64])
-        self._w = (None if weights is None
-                   else (ctypes.c_float * max(1, len(weights)))(*map(float, weights)))
-        self._plans = (_P * 1)(self.plan.handle.value)
-        self.io = FaShardIO()
-        self.io.c32 = ctypes.cast(self._a32, _P)
-        self.io.c64 = ctypes.cast(self._a64, _P) if layout.i64_numel else None
-        self.io.weights = ctypes.cast(self._w, _P) if self._w is not None else None
-        self.io.out32 = out32.data_ptr()
-        self.io.out64 = out64.data_ptr() if layout.i64_numel else None
-        self._keep = (local32, local64, out32, out64)
-
-    def step(self, stream=None) -> None:
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        self.io.stream = s
-        _lib.check(lib().fa_reduce_striped(self._plans, 1, ctypes.byref(self.io), self.root),
-                   "fa_reduce_striped")
-
-
-class ChainPlan:
-    """This rank's chained-mode plan (vector-tile chunk plans, the state
-    planes, the raw scalar-column gather buffers)."""
-
-    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int],
-                 nchunks: int = 16):
-        a32, n32, a64, n64 = _segs(layout)
-        c = (_I * len(counts))(*map(int, counts))
-        h = _P()
-        _lib.check(lib().fa_chain_plan_create(comm.handle, a32, n32, int(layout.f32_numel), a64,
-                                              n64, int(layout.i64_numel), c, int(nchunks),
-                                              _lib.FA_PLAN_GAPS_ARE_PADDING, ctypes.byref(h)),
-                   "fa_chain_plan_create")
-        self.handle = h
-        self.comm = comm
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None and h.value:
-            try:
-                lib().fa_chain_plan_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
+        self._bind(StripePlan, (nchunks,), layout, local32, local64, n_total, out32, out64, comm,
+                   final, root, weights, counts)
 
 
 class NativeChainedAggregator(NativeShardedAggregator):
@@ -499,64 +504,15 @@ class NativeChainedAggregator(NativeShardedAggregator):
     (train_feddct.py:42-50's order over all slots).  ``final="reduce"``: the
     result lands on ``root`` (cheapest when root is the last rank holding
     clients); ``"allreduce"``: on every rank."""
+    _entry = "fa_reduce_chained"
 
     def __init__(self, layout: BucketLayout, local32: List[torch.Tensor],
                  local64: List[torch.Tensor], n_total: int, out32: torch.Tensor,
                  out64: torch.Tensor, comm: Comm, nchunks: int = 16, final: str = "reduce",
                  root: int = 0, weights: Optional[Sequence[float]] = None,
                  counts: Optional[Sequence[int]] = None):
-        if final not in ("reduce", "allreduce"):
-            raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
-        world, rank, _ = comm.info()
-        if counts is None:
-            counts = [b - a for a, b in (shard_range(n_total, world, r) for r in range(world))]
-        if len(local32) != counts[rank] or sum(counts) != n_total:
-            raise ValueError(f"rank {rank} holds {len(local32)} clients, shard is {counts[rank]}")
-        self.plan = ChainPlan(comm, layout, counts, nchunks)
-        self.root = root if final == "reduce" else -1
-        self._a32 = _lib.ptr_array([t.data_ptr() for t in local32])
-        self._a64 = _lib.ptr_array([t.data_ptr() for t in local64])
-        self._w = (None if weights is None
-                   else (ctypes.c_float * max(1, len(weights)))(*map(float, weights)))
-        self._plans = (_P * 1)(self.plan.handle.value)
-        self.io = FaShardIO()
-        self.io.c32 = ctypes.cast(self._a32, _P)
-        self.io.c64 = ctypes.cast(self._a64, _P) if layout.i64_numel else None
-        self.io.weights = ctypes.cast(self._w, _P) if self._w is not None else None
-        self.io.out32 = out32.data_ptr()
-        self.io.out64 = out64.data_ptr() if layout.i64_numel else None
-        self._keep = (local32, local64, out32, out64)
-
-    def step(self, stream=None) -> None:
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        self.io.stream = s
-        _lib.check(lib().fa_reduce_chained(self._plans, 1, ctypes.byref(self.io), self.root),
-                   "fa_reduce_chained")
-
-
-class BlockPlan:
-    """This rank's blocked-mode plan (block-sum planes, the stripe it owns,
-    relay rows, the raw scalar-column gather buffers)."""
-
-    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int]):
-        a32, n32, a64, n64 = _segs(layout)
-        c = (_I * len(counts))(*map(int, counts))
-        h = _P()
-        _lib.check(lib().fa_block_plan_create(comm.handle, a32, n32, int(layout.f32_numel), a64,
-                                              n64, int(layout.i64_numel), c,
-                                              _lib.FA_PLAN_GAPS_ARE_PADDING, ctypes.byref(h)),
-                   "fa_block_plan_create")
-        self.handle = h
-        self.comm = comm
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None and h.value:
-            try:
-                lib().fa_block_plan_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
+        self._bind(ChainPlan, (nchunks,), layout, local32, local64, n_total, out32, out64, comm,
+                   final, root, weights, counts)
 
 
 class NativeBlockedAggregator(NativeChainedAggregator):
@@ -567,73 +523,15 @@ class NativeBlockedAggregator(NativeChainedAggregator):
     block order — train_feddct.py:42-50's order over all slots, without the
     chained round's rank-to-rank pipeline.  Same arguments as the chained
     form; requires every 16-slot block to lie on at most two ranks."""
+    _entry = "fa_reduce_blocked"
 
     def __init__(self, layout: BucketLayout, local32: List[torch.Tensor],
                  local64: List[torch.Tensor], n_total: int, out32: torch.Tensor,
                  out64: torch.Tensor, comm: Comm, final: str = "reduce", root: int = 0,
                  weights: Optional[Sequence[float]] = None,
                  counts: Optional[Sequence[int]] = None):
-        if final not in ("reduce", "allreduce"):
-            raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
-        world, rank, _ = comm.info()
-        if counts is None:
-            counts = [b - a for a, b in (shard_range(n_total, world, r) for r in range(world))]
-        if len(local32) != counts[rank] or sum(counts) != n_total:
-            raise ValueError(f"rank {rank} holds {len(local32)} clients, shard is {counts[rank]}")
-        self.plan = BlockPlan(comm, layout, counts)
-        self.root = root if final == "reduce" else -1
-        self._a32 = _lib.ptr_array([t.data_ptr() for t in local32])
-        self._a64 = _lib.ptr_array([t.data_ptr() for t in local64])
-        self._w = (None if weights is None
-                   else (ctypes.c_float * max(1, len(weights)))(*map(float, weights)))
-        self._plans = (_P * 1)(self.plan.handle.value)
-        self.io = FaShardIO()
-        self.io.c32 = ctypes.cast(self._a32, _P)
-        self.io.c64 = ctypes.cast(self._a64, _P) if layout.i64_numel else None
-        self.io.weights = ctypes.cast(self._w, _P) if self._w is not None else None
-        self.io.out32 = out32.data_ptr()
-        self.io.out64 = out64.data_ptr() if layout.i64_numel else None
-        self._keep = (local32, local64, out32, out64)
-
-    def step(self, stream=None) -> None:
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        self.io.stream = s
-        _lib.check(lib().fa_reduce_blocked(self._plans, 1, ctypes.byref(self.io), self.root),
-                   "fa_reduce_blocked")
-
-
-class MultiPlan:
-    """This rank's plan of the default round (fa_multi_plan_create): the form
-    and chunk count the cost model picks for ``counts`` on ``layout``
-    (``mode``, ``nchunks`` name them); ``root_all``: the model's root is
-    every rank (FA_MULTI_ROOT_ALL)."""
-
-    def __init__(self, comm: Comm, layout: BucketLayout, counts: Sequence[int],
-                 nchunks: int = 0, exact: bool = True, root_all: bool = False):
-        a32, n32, a64, n64 = _segs(layout)
-        c = (_I * len(counts))(*map(int, counts))
-        h = _P()
-        _lib.check(lib().fa_multi_plan_create(comm.handle, a32, n32, int(layout.f32_numel), a64,
-                                              n64, int(layout.i64_numel), c, int(nchunks),
-                                              _lib.FA_PLAN_GAPS_ARE_PADDING,
-                                              _mflags(exact, root_all),
-                                              ctypes.byref(h)), "fa_multi_plan_create")
-        self.handle = h
-        self.comm = comm
-        m, k = _I(), _I()
-        _lib.check(lib().fa_multi_plan_mode(h, ctypes.byref(m)), "fa_multi_plan_mode")
-        _lib.check(lib().fa_multi_plan_chunks(h, ctypes.byref(k)), "fa_multi_plan_chunks")
-        self.mode = MODE_NAMES[m.value]
-        self.nchunks = k.value
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None and h.value:
-            try:
-                lib().fa_multi_plan_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
+        self._bind(BlockPlan, (), layout, local32, local64, n_total, out32, out64, comm, final,
+                   root, weights, counts)
 
 
 class NativeAggregator(NativeShardedAggregator):
@@ -654,41 +552,14 @@ class NativeAggregator(NativeShardedAggregator):
     puts the result on ``root`` (default: the last rank holding slots, where
     the chained round ends), ``"allreduce"`` on every rank; ``weights``: this
     rank's fp32 client weights (weighted rounds are exact too)."""
+    _entry = "fa_reduce_multi"
 
     def __init__(self, layout: BucketLayout, local32: List[torch.Tensor],
                  local64: List[torch.Tensor], n_total: int, out32: torch.Tensor,
                  out64: torch.Tensor, comm: Comm, final: str = "reduce",
                  root: Optional[int] = None, weights: Optional[Sequence[float]] = None,
                  counts: Optional[Sequence[int]] = None, exact: bool = True, nchunks: int = 0):
-        if final not in ("reduce", "allreduce"):
-            raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
-        world, rank, _ = comm.info()
-        if counts is None:
-            counts = [b - a for a, b in (shard_range(n_total, world, r) for r in range(world))]
-        if len(counts) != world or len(local32) != counts[rank] or sum(counts) != n_total:
-            raise ValueError(f"rank {rank} holds {len(local32)} clients, shard is "
-                             f"{counts[rank] if rank < len(counts) else '?'}")
-        self.plan = MultiPlan(comm, layout, counts, nchunks, exact, root_all=final != "reduce")
+        self._bind(MultiPlan, (nchunks, exact, final != "reduce"), layout, local32, local64,
+                   n_total, out32, out64, comm, final, root, weights, counts, world_counts=True)
         self.mode = self.plan.mode
         self.nchunks = self.plan.nchunks
-        if root is None:
-            root = max(r for r in range(world) if counts[r] > 0)
-        self.root = root if final == "reduce" else -1
-        self._a32 = _lib.ptr_array([t.data_ptr() for t in local32])
-        self._a64 = _lib.ptr_array([t.data_ptr() for t in local64])
-        self._w = (None if weights is None
-                   else (ctypes.c_float * max(1, len(weights)))(*map(float, weights)))
-        self._plans = (_P * 1)(self.plan.handle.value)
-        self.io = FaShardIO()
-        self.io.c32 = ctypes.cast(self._a32, _P)
-        self.io.c64 = ctypes.cast(self._a64, _P) if layout.i64_numel else None
-        self.io.weights = ctypes.cast(self._w, _P) if self._w is not None else None
-        self.io.out32 = out32.data_ptr()
-        self.io.out64 = out64.data_ptr() if layout.i64_numel else None
-        self._keep = (local32, local64, out32, out64)
-
-    def step(self, stream=None) -> None:
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        self.io.stream = s
-        _lib.check(lib().fa_reduce_multi(self._plans, 1, ctypes.byref(self.io), self.root),
-                   "fa_reduce_multi")

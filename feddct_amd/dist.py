@@ -61,6 +61,16 @@ def shard_range(n_total: int, world: int, rank: int):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def shard_counts(n_total: int, world: int) -> List[int]:
+    """Slots per rank under ``shard_range``."""
+    return [b - a for a, b in (shard_range(n_total, world, r) for r in range(world))]
+
+
+def check_final(final: str) -> None:
+    if final not in ("reduce", "allreduce"):
+        raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
+
+
 def cascade_lp(n: int) -> int:
     """torch's cascade level step for n rows (16 below 2**16 rows)."""
     return max(4, (int(n - 1).bit_length() if n > 1 else 0) // 4)
@@ -181,7 +191,23 @@ def chunk_segments(layout: BucketLayout, nchunks: int):
     return out
 
 
-class HipBackend:
+class _HipI64:
+    """What the Hip* backends share: the current stream, and the exact int64
+    reduce over ``self.plan64`` (None: nothing to reduce)."""
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def reduce_i64(self, clients64: Sequence[torch.Tensor], out64: torch.Tensor):
+        if self.plan64 is None:
+            return
+        L = self._lib
+        a = L.ptr_array([t.data_ptr() for t in clients64])
+        L.check(L.lib.fa_reduce(self.plan64.handle, None, a, len(clients64), None, None,
+                                out64.data_ptr(), 0, self._stream()), "fa_reduce(i64)")
+
+
+class HipBackend(_HipI64):
     """fa_reduce / fa_div_f32 on the current device and stream."""
 
     def __init__(self, layout: BucketLayout, chunks, n_local: int, n_total: int):
@@ -190,9 +216,6 @@ class HipBackend:
         self.plans = [_lib.Plan(s, layout.f32_numel) for s, _, _ in chunks]
         self.plan64 = (_lib.Plan(np.zeros((0, 2), np.int64), 0, layout.segs64, layout.i64_numel)
                        if layout.i64_numel else None)
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def partial_sum(self, chunk_index, clients32: Sequence[torch.Tensor], out: torch.Tensor):
         L = self._lib
@@ -205,14 +228,6 @@ class HipBackend:
         L = self._lib
         L.check(L.lib.fa_div_f32(x.data_ptr(), float(d), out.data_ptr(), x.numel(),
                                  self._stream()), "fa_div_f32")
-
-    def reduce_i64(self, clients64: Sequence[torch.Tensor], out: torch.Tensor):
-        if self.plan64 is None:
-            return
-        L = self._lib
-        a = L.ptr_array([t.data_ptr() for t in clients64])
-        L.check(L.lib.fa_reduce(self.plan64.handle, None, a, len(clients64), None, None,
-                                out.data_ptr(), 0, self._stream()), "fa_reduce(i64)")
 
 
 class ShardedAggregator:
@@ -232,8 +247,7 @@ class ShardedAggregator:
                  local64: List[torch.Tensor], n_total: int, out32: torch.Tensor,
                  out64: torch.Tensor, nchunks: int = 8, backend=None, group=None,
                  final: str = "reduce", root: int = 0, exchange: str = "reduce"):
-        if final not in ("reduce", "allreduce"):
-            raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
+        check_final(final)
         if exchange not in ("reduce", "rs_gather"):
             raise ValueError(f"exchange must be 'reduce' or 'rs_gather', not {exchange!r}")
         self.exchange = exchange
@@ -338,7 +352,7 @@ class ShardedAggregator:
 # --------------------------------------------------------------------------
 # Exact mode: element (column) stripes.
 # --------------------------------------------------------------------------
-class HipStripeBackend:
+class HipStripeBackend(_HipI64):
     """Stripe-chunk reductions with the HIP kernel over tile-subset plans
     (one per chunk of this rank's stripe)."""
 
@@ -360,18 +374,9 @@ class HipStripeBackend:
         L = self._lib
         ptrs = [t.data_ptr() - 4 * base for t, base in sources]
         w = None if weights is None else (ctypes.c_float * len(weights))(*map(float, weights))
-        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         L.check(L.lib.fa_reduce(self.plans[c].handle, L.ptr_array(ptrs), None, len(ptrs), w,
-                                out32.data_ptr(), None, 0, s), "fa_reduce(stripe chunk)")
-
-    def reduce_i64(self, clients64, out64: torch.Tensor):
-        if self.plan64 is None:
-            return
-        L = self._lib
-        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        L.check(L.lib.fa_reduce(self.plan64.handle, None,
-                                L.ptr_array([t.data_ptr() for t in clients64]), len(clients64),
-                                None, None, out64.data_ptr(), 0, s), "fa_reduce(i64)")
+                                out32.data_ptr(), None, 0, self._stream()),
+                "fa_reduce(stripe chunk)")
 
 
 class StripedAggregator:
@@ -401,8 +406,7 @@ class StripedAggregator:
                  out64: torch.Tensor, group=None, backend=None, final: str = "allreduce",
                  root: int = 0, nchunks: int = 4, counts: Optional[Sequence[int]] = None):
         from .partition import i64_tiles, layout_tiles, stripe_chunks
-        if final not in ("reduce", "allreduce"):
-            raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
+        check_final(final)
         self.final = final
         self.root = root if final == "reduce" else -1
         self.layout = layout
@@ -412,8 +416,7 @@ class StripedAggregator:
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
         if counts is None:
-            counts = [b - a for a, b in (shard_range(n_total, self.world, r)
-                                         for r in range(self.world))]
+            counts = shard_counts(n_total, self.world)
         self.counts = [int(c) for c in counts]
         if len(self.counts) != self.world or sum(self.counts) != n_total:
             raise ValueError(f"counts {self.counts} do not shard {n_total} slots over "
@@ -554,7 +557,7 @@ def chain_levels(rows: int, n_total: int) -> int:
     return m
 
 
-class HipChainBackend:
+class HipChainBackend(_HipI64):
     """fa_reduce_chain over the vector-tile chunks; the raw scalar columns
     (compact tail plan + int64 plan) reduced with fa_reduce."""
 
@@ -569,9 +572,6 @@ class HipChainBackend:
                        if len(t64) else None)
         self.tout = None
 
-    def _s(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def chain(self, c, clients32, row0, n_total, state, state_in, out, plane, weights=None):
         L = self._lib
         ch = L.FaChain(row0, n_total, state.data_ptr() if state_in else None,
@@ -580,8 +580,8 @@ class HipChainBackend:
         L.check(L.lib.fa_reduce_chain(self.plans[c].handle,
                                       L.ptr_array([t.data_ptr() for t in clients32]),
                                       len(clients32), w, ctypes.byref(ch),
-                                      out.data_ptr() if out is not None else None, 0, self._s()),
-                "fa_reduce_chain")
+                                      out.data_ptr() if out is not None else None, 0,
+                                      self._stream()), "fa_reduce_chain")
 
     def tails(self, rows32, tidx, out32, weighted):
         L = self._lib
@@ -589,16 +589,9 @@ class HipChainBackend:
             self.tout = torch.zeros(max(64, -(-len(tidx) // 64) * 64), device=out32.device)
         L.check(L.lib.fa_reduce(self.plan_t32.handle, L.ptr_array([r.data_ptr() for r in rows32]),
                                 None, len(rows32), None, self.tout.data_ptr(), None,
-                                L.FA_F_SUM_ONLY if weighted else 0, self._s()), "fa_reduce(tails)")
+                                L.FA_F_SUM_ONLY if weighted else 0, self._stream()),
+                "fa_reduce(tails)")
         out32[tidx] = self.tout[:len(tidx)]
-
-    def reduce_i64(self, clients64, out64):
-        if self.plan64 is None:
-            return
-        L = self._lib
-        L.check(L.lib.fa_reduce(self.plan64.handle, None,
-                                L.ptr_array([t.data_ptr() for t in clients64]), len(clients64),
-                                None, None, out64.data_ptr(), 0, self._s()), "fa_reduce(i64)")
 
 
 class ChainAggregator:
@@ -619,8 +612,7 @@ class ChainAggregator:
                  out64: torch.Tensor, group=None, backend=None, final: str = "reduce",
                  root: int = 0, nchunks: int = 16, counts: Optional[Sequence[int]] = None):
         from .partition import chain_cut
-        if final not in ("reduce", "allreduce"):
-            raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
+        check_final(final)
         self.layout, self.n_total = layout, n_total
         self.out32, self.out64 = out32, out64
         self.group = group
@@ -628,8 +620,7 @@ class ChainAggregator:
         self.rank = dist.get_rank(group)
         self.root = root if final == "reduce" else -1
         if counts is None:
-            counts = [b - a for a, b in (shard_range(n_total, self.world, r)
-                                         for r in range(self.world))]
+            counts = shard_counts(n_total, self.world)
         self.counts = list(counts)
         self.first = [sum(self.counts[:r]) for r in range(self.world)]
         self.finisher = max(r for r in range(self.world) if self.counts[r] > 0)
@@ -763,11 +754,10 @@ class Aggregator:
                  counts: Optional[Sequence[int]] = None, exact: bool = True,
                  native: Optional[bool] = None, backend=None, nchunks: Optional[int] = None,
                  stripe_backend=None):
-        if final not in ("reduce", "allreduce"):
-            raise ValueError(f"final must be 'reduce' or 'allreduce', not {final!r}")
+        check_final(final)
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         if counts is None:
-            counts = [b - a for a, b in (shard_range(n_total, world, r) for r in range(world))]
+            counts = shard_counts(n_total, world)
         counts = [int(c) for c in counts]
         if len(counts) != world or sum(counts) != n_total or len(local32) != counts[rank]:
             raise ValueError(f"rank {rank} holds {len(local32)} clients; counts {counts} "
@@ -779,8 +769,7 @@ class Aggregator:
         if not exact:
             if weights is not None:
                 raise ValueError("the re-associated e1 round is unweighted")
-            if counts != [b - a for a, b in (shard_range(n_total, world, r)
-                                             for r in range(world))]:
+            if counts != shard_counts(n_total, world):
                 raise ValueError("the e1 round takes shard_range shards")
             self._agg = ShardedAggregator(layout, local32, local64, n_total, out32, out64,
                                           nchunks=nchunks or 8, backend=backend, group=group,
