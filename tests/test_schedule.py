@@ -467,3 +467,60 @@ def test_blocked_and_chained_scalar_only_layout():
                 src = bufs[r]["OUT64"] if s.kind == "i64" else bufs[r]["OUT"]
                 got = src[s.offset:s.offset + s.numel].reshape(s.shape)
                 assert got.tobytes() == np.asarray(want[s.key]).tobytes(), (mode, r, s.key)
+
+
+# The counts, roots and weight vectors the GPU loopback runs under special
+# values (tests/test_gpu_loopback.py), replayed here with the oracle as the
+# arithmetic: the schedule half of those rounds, so a difference on the GPU is
+# the executor's.
+SPECIAL_COUNTS = [[10, 10], [7, 0, 13], [16, 16, 1], [100, 156, 44]]
+
+
+def _special_states(man, n, seed):
+    """Client states over ``man``: every fp32 key's columns carry the nine
+    specials.py patterns (phase = the key's index), int64 keys the generator's."""
+    import specials
+    rng = np.random.default_rng(seed)
+    cols = []
+    for j, e in enumerate(man["keys"]):
+        shape = tuple(e["shape"])
+        m = int(np.prod(shape)) if shape else 1
+        if e["dtype"] == "int64":
+            cols.append([synth.gen_i64(j, m, c).reshape(shape) for c in range(n)])
+        else:
+            x = specials.pattern_matrix(n, m, j, rng)
+            cols.append([x[c].reshape(shape) for c in range(n)])
+    return [[(e["key"], cols[j][c]) for j, e in enumerate(man["keys"])] for c in range(n)]
+
+
+@pytest.mark.parametrize("counts", SPECIAL_COUNTS)
+@pytest.mark.parametrize("root", [0, -1])
+@pytest.mark.parametrize("wmode", ["mean", "w1", "w2"])
+@pytest.mark.parametrize("mode", [C.FA_MODE_CHAINED, C.FA_MODE_STRIPED, C.FA_MODE_BLOCKED])
+def test_exact_schedules_under_special_values(mode, counts, root, wmode):
+    """inf, NaN, -0.0, subnormals, overflowing and cancelling columns, and
+    weights that are 0, subnormal, negative and inf, through the chained,
+    striped and blocked schedules: every result rank holds the single-process
+    reference's bits (NaNs where it has NaNs), int64 keys included."""
+    import specials
+    from helpers import bits_equal
+    layout = BucketLayout.from_manifest(MAN)
+    n = sum(counts)
+    states = _special_states(MAN, n, 977 * n + len(counts))
+    c32, c64 = _buckets(layout, states)
+    w = specials.mode_weights(n, wmode)
+    _, tiles = layout_tiles(layout)
+    scheds = [C.describe(mode, layout, counts, r, nchunks=3, root=root, weighted=w is not None)
+              for r in range(len(counts))]
+    with np.errstate(all="ignore"):
+        bufs = Sim(layout, tiles, counts, c32, c64, w, root).run(scheds)
+        want = {}
+        for j, (k, _) in enumerate(states[0]):
+            x = np.stack([np.asarray(s[j][1]) for s in states])
+            want[k] = (O.mean_i64_trunc(x) if x.dtype == np.int64
+                       else specials.oracle(x, wmode, w))
+    for r in _result_ranks(len(counts), root):
+        for s in layout.slots:
+            src = bufs[r]["OUT64"] if s.kind == "i64" else bufs[r]["OUT"]
+            got = src[s.offset:s.offset + s.numel].reshape(s.shape)
+            assert bits_equal(got, np.asarray(want[s.key])), (r, s.key)
