@@ -63,6 +63,7 @@ EXPORTS = [
     "fa_plan_balance_host", "fa_plan_launch_shape", "fa_plan_launch_form",
     "fa_plan_create_elem", "fa_plan_build_host_elem", "fa_plan_elem",
     "fa_plan_create_elem_out", "fa_plan_out_elem",
+    "fa_plan_create_from_tiles_elem", "fa_narrow_f32",
 ]
 
 
@@ -120,6 +121,9 @@ def _load():
         "fa_plan_get_info": (_I, [_P, ctypes.POINTER(FaPlanInfo)]),
         "fa_plan_create_from_tiles": (_I, [_P, _I, _I64, _I64, _I, ctypes.c_uint,
                                            ctypes.POINTER(_P)]),
+        "fa_plan_create_from_tiles_elem": (_I, [_P, _I, _I64, _I64, _I, ctypes.c_uint, _I, _I,
+                                                ctypes.POINTER(_P)]),
+        "fa_narrow_f32": (_I, [_P, _P, _I, _I64, _P]),
         "fa_reduce": (_I, [_P, _P, _P, _I, _P, _P, _P, ctypes.c_uint, _P]),
         "fa_table_bytes": (ctypes.c_size_t, [_I]),
         "fa_plan_balance_host": (_I, [_P, _I, _I, _I, _I, _P, _I]),
@@ -291,6 +295,31 @@ class Plan:
         info = FaPlanInfo()
         check(lib.fa_plan_get_info(h, ctypes.byref(info)), "fa_plan_get_info")
         self.info = {f: getattr(info, f) for f, _ in FaPlanInfo._fields_}
+
+    @classmethod
+    def from_tiles(cls, tiles, f32_numel, i64_numel=0, tile_elems=0,
+                   flags=FA_PLAN_GAPS_ARE_PADDING, elem=FA_ELEM_F32, out_elem=None):
+        """A plan over an explicit subset ``tiles`` [(start, count, kind)] of a
+        layout's table, of any element type (fa_plan_create_from_tiles_elem):
+        fp32, 16-bit (``elem`` FA_ELEM_F16 / FA_ELEM_BF16), or mixed
+        (``out_elem`` FA_ELEM_F32 over 16-bit clients)."""
+        self = cls.__new__(cls)
+        self.elem = int(elem)
+        self.out_elem = self.elem if out_elem is None else int(out_elem)
+        tiles = np.asarray(tiles, np.int64).reshape(-1, 3)
+        arr = (FaTileDesc * max(1, len(tiles)))()
+        for i, (s, c, k) in enumerate(tiles):
+            arr[i].start, arr[i].count, arr[i].kind = int(s), int(c), int(k)
+        h = ctypes.c_void_p()
+        check(lib.fa_plan_create_from_tiles_elem(arr, len(tiles), int(f32_numel), int(i64_numel),
+                                                 int(tile_elems), flags, self.elem, self.out_elem,
+                                                 ctypes.byref(h)),
+              "fa_plan_create_from_tiles_elem")
+        self.handle = h
+        info = FaPlanInfo()
+        check(lib.fa_plan_get_info(h, ctypes.byref(info)), "fa_plan_get_info")
+        self.info = {f: getattr(info, f) for f, _ in FaPlanInfo._fields_}
+        return self
 
     def launch_shape(self, n, weighted=False):
         """(tiles, resident-workgroup slots) a plain fa_reduce call with n

@@ -22,7 +22,9 @@ Where the work runs: client state is bound once into flat device buckets
 reduced by ONE launch of the HIP kernel (csrc/fedagg.hip), and the broadcast
 is a second launch over the same tile table (FA_F_BCAST).  Modules living in host memory (the reference's CPU configuration)
 are bound to pinned host buckets and staged through device buckets
-(host-inclusive path).  There is no CPU arithmetic fallback.
+(host-inclusive path); host-resident fp16 / bf16 modules keep
+16-bit buckets there too.  There is no CPU arithmetic
+fallback.
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ from array import array
 from . import _lib, slab
 from . import arena as _arena
 from .arena import ModuleArena, get_arena
-from .layout import BucketLayout, native16_dtype
+from .layout import H16_DTYPES, BucketLayout, native16_dtype
 
 __all__ = ["server_aggregate", "server_aggregate_split", "aggregate_weighted", "client_weights",
            "Engine", "engine", "set_summation_order", "summation_order"]
@@ -60,6 +62,24 @@ def _require_gpu():
 # bucket's storage, and the tensors while the GPU reduces (cfg5's 9,800: 16 us
 # that would otherwise precede the launch; shim.cpp bound_round).
 BOUND_PRECHECK_MAX = 4096
+
+
+def _state_tensors(module: torch.nn.Module):
+    """arena.state_owners as a generator of (dict, name): a caller that
+    stops at the first tensor that settles its question walks no further."""
+    for m in module.modules():
+        for n, p in m._parameters.items():
+            if p is not None:
+                yield m._parameters, n
+        for n, b in m._buffers.items():
+            if b is not None and n not in m._non_persistent_buffers_set:
+                yield m._buffers, n
+
+
+def _first_tensor(module: torch.nn.Module):
+    for d, n in _state_tensors(module):
+        return d[n]
+    return None
 
 
 class _RoundBinding:
@@ -301,6 +321,44 @@ class Engine:
         kind, h16 = self._round_dtypes(global_model, client_models)
         return h16 if kind == "mixed" else None
 
+    def _host_round_dtypes(self, global_model, client_models):
+        """_round_dtypes' answer for a round whose modules all sit in host
+        memory (the one placement _round_dtypes itself refuses, and
+        prox.ProximalTerm with it): (kind, dtype) when the global and every
+        client are on the CPU, every non-int64 key of every client has the
+        one 16-bit dtype, and the global's non-int64 keys are all of that
+        dtype ("native") or all fp32 ("mixed"); else (None, None).  The
+        summation order is not looked at: a host round takes torch's CPU
+        order whatever set_summation_order says.  The round then runs through
+        the host pipeline on 16-bit buckets (_reduce_host) instead of being
+        staged key by key through pinned fp32 ones."""
+        # the clients first: an fp32 federation (the common host round) is
+        # told apart at its first tensor, before any module tree is walked whole
+        gdts, cdts = set(), set()
+        for i, m in enumerate((*client_models, global_model)):
+            last = i == len(client_models)
+            for d, name in _state_tensors(m):
+                t = d[name]
+                if t.device.type != "cpu":
+                    return None, None
+                if t.dtype != torch.int64:
+                    if last:
+                        gdts.add(t.dtype)
+                    elif t.dtype not in H16_DTYPES:
+                        return None, None
+                    else:
+                        cdts.add(t.dtype)
+            if len(cdts) > 1 or len(gdts) > 1:
+                return None, None
+        h16 = native16_dtype(cdts)
+        if h16 is None:
+            return None, None
+        if gdts <= cdts:
+            return "native", h16
+        if gdts == {torch.float32}:
+            return "mixed", h16
+        return None, None
+
     def round_layouts(self, global_model: torch.nn.Module,
                       client_models: Sequence[torch.nn.Module]):
         """(global's layout, clients' layout) a round over these modules is
@@ -310,7 +368,14 @@ class Engine:
         the 16-bit layout's element offsets) and the clients the native
         16-bit layout of the same keys in their dtype."""
         lay = self.layout_of(global_model)
-        kind, h16 = self._round_dtypes(global_model, client_models)
+        # _round_dtypes qualifies only rounds whose every tensor is on one
+        # GPU: with a client tensor in host memory its answer is known, and
+        # the host qualification (the same two layouts) is asked instead
+        t = _first_tensor(client_models[0]) if len(client_models) else None
+        if t is not None and t.device.type == "cpu":
+            kind, h16 = self._host_round_dtypes(global_model, client_models)
+        else:
+            kind, h16 = self._round_dtypes(global_model, client_models)
         if kind == "mixed":
             if not lay.master16:
                 lay = BucketLayout.from_state_dict(global_model.state_dict(), master16=True)
@@ -446,7 +511,7 @@ class Engine:
                 ga.f32.copy_(o32)
                 ga.i64.copy_(o64)
         else:
-            self._reduce_host(layout, ga, cas, weights, fuse_bcast)
+            self._reduce_host(glayout, layout, ga, cas, weights, fuse_bcast)
         ga.unpack()
         ga.mark_written()
         if broadcast and not fuse_bcast:
@@ -535,19 +600,25 @@ class Engine:
                      out64.data_ptr(), flags, dev)
         return plan
 
-    def _reduce_host(self, layout, ga: ModuleArena, cas: List[ModuleArena], weights, fuse):
+    def _reduce_host(self, glayout, layout, ga: ModuleArena, cas: List[ModuleArena], weights,
+                     fuse):
         """Host-resident state (the reference's CPU configuration): the
         chunked H2D / reduce / D2H pipeline (pipeline.py) over the modules'
         pinned arenas; the broadcast fans each downloaded chunk out to the
-        clients' host buckets on the CPU while later chunks upload."""
+        clients' host buckets on the CPU while later chunks upload.
+        ``layout`` is the clients': fp32, or native 16-bit (2 B per element
+        over PCIe); ``glayout`` the global's — the same object, or in a mixed
+        round the master layout, whose fp32 bucket takes the unrounded mean
+        while the clients get its rounding (HostPipeline ``master``)."""
         from .pipeline import HostPipeline
         n = len(cas)
         dev = (ga.device if ga.device.type == "cuda"
                else torch.device("cuda", torch.cuda.current_device()))
-        key = (layout.signature, dev.index, n)
+        master = glayout is not layout
+        key = (layout.signature, dev.index, n) + (("<master>",) if master else ())
         pipe = self._pipes.get(key)
         if pipe is None:
-            pipe = self._pipes[key] = HostPipeline(layout, n, dev)
+            pipe = self._pipes[key] = HostPipeline(layout, n, dev, master=master)
         bc32 = [c.f32 for c in cas] if fuse else []
         bc64 = [c.i64 for c in cas] if fuse else []
         pipe.run([c.f32 for c in cas], [c.i64 for c in cas], ga.f32, ga.i64, bc32, bc64,

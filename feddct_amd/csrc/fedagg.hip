@@ -1253,18 +1253,33 @@ int fa_plan_create_order(const fa_seg* seg32, int nseg32, int64_t f32_numel, con
   return FA_OK;
 }
 
-int fa_plan_create_from_tiles(const fa_tile_desc* tiles, int ntiles, int64_t f32_numel,
-                              int64_t i64_numel, int tile_elems, unsigned flags,
-                              fa_plan** out) {
-  if (!out) return set_err(FA_E_INVAL, "fa_plan_create_from_tiles: out is NULL");
+namespace {
+// One body behind fa_plan_create_from_tiles and ..._from_tiles_elem (`who`,
+// in the messages).  A 16-bit or mixed subset plan is cut from
+// fa_plan_build_host_elem's table: vectors of 8 elements, tiles of 2048 or
+// 4096, launched by the 16-bit kernels as a segment plan's table is; it
+// covers no bucket (flat_bcast stays false), so fa_reduce refuses its
+// broadcast.  Every refusal returns before the first device call.
+int plan_from_tiles(const char* who, const fa_tile_desc* tiles, int ntiles, int64_t f32_numel,
+                    int64_t i64_numel, int tile_elems, unsigned flags, int elem, int out_elem,
+                    fa_plan** out) {
+  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
   *out = nullptr;
-  int rc = fa_host::check_flags("fa_plan_create_from_tiles", flags);
+  int rc = fa_host::check_flags(who, flags);
   if (rc) return rc;
-  if (ntiles < 0 || (ntiles > 0 && !tiles))
-    return set_err(FA_E_INVAL, "fa_plan_create_from_tiles: bad tile array");
-  if (tile_elems == 0) tile_elems = 4 * kBlock * kDefaultU;
-  if (tile_elems != 4 * kBlock && tile_elems != 8 * kBlock && tile_elems != 16 * kBlock)
-    return set_err(FA_E_INVAL, "tile_elems must be 1024, 2048 or 4096 (got %d)", tile_elems);
+  if (ntiles < 0 || (ntiles > 0 && !tiles)) return set_err(FA_E_INVAL, "%s: bad tile array", who);
+  const bool h16 = elem != FA_ELEM_F32;
+  const int valign = h16 ? fa_h16::kVec : 4;
+  if (h16) {
+    if (tile_elems == 0) tile_elems = fa_h16::kDefaultU * fa_h16::kTile;
+    if (tile_elems != fa_h16::kTile && tile_elems != 2 * fa_h16::kTile)
+      return set_err(FA_E_INVAL, "%s: a 16-bit plan's tile_elems must be 2048 or 4096 (got %d)",
+                     who, tile_elems);
+  } else {
+    if (tile_elems == 0) tile_elems = 4 * kBlock * kDefaultU;
+    if (tile_elems != 4 * kBlock && tile_elems != 8 * kBlock && tile_elems != 16 * kBlock)
+      return set_err(FA_E_INVAL, "tile_elems must be 1024, 2048 or 4096 (got %d)", tile_elems);
+  }
   fa_plan_info in{};
   in.f32_numel = f32_numel;
   in.i64_numel = i64_numel;
@@ -1279,8 +1294,8 @@ int fa_plan_create_from_tiles(const fa_tile_desc* tiles, int ntiles, int64_t f32
       return set_err(FA_E_INVAL, "tile %d: kind %d [%lld,+%d) invalid", i, d.kind,
                      (long long)d.start, d.count);
     if (d.kind == K_F32_VEC) {
-      if (d.start % 4 || d.count % 4 || d.count > tile_elems)
-        return set_err(FA_E_INVAL, "tile %d: vector tile must be 4-aligned and <= %d", i,
+      if (d.start % valign || d.count % valign || d.count > tile_elems)
+        return set_err(FA_E_INVAL, "tile %d: vector tile must be %d-aligned and <= %d", i, valign,
                        tile_elems);
       vec.push_back(Tile{d.start, d.count, d.kind});
       in.cascade_elems += d.count;
@@ -1292,22 +1307,47 @@ int fa_plan_create_from_tiles(const fa_tile_desc* tiles, int ntiles, int64_t f32
   }
   std::vector<Tile> t(sc);
   t.insert(t.end(), vec.begin(), vec.end());
-  rc = fa_host::check_disjoint(t, "fa_plan_create_from_tiles");
+  rc = fa_host::check_disjoint(t, who);
   if (rc) return rc;
   in.ntiles = (int32_t)t.size();
   in.ntiles_cascade = (int32_t)vec.size();
   in.ntiles_tail = (int32_t)sc.size();
   PlanPtr p(new fa_plan());
   p->info = in;
-  p->vec_u = tile_elems / (4 * kBlock);
+  p->elem = elem;
+  p->out_elem = out_elem;
+  p->vec_u = tile_elems / (h16 ? fa_h16::kTile : 4 * kBlock);
   p->flags = flags | FA_PLAN_TUNE_NO_BALANCE;  // the caller's tiles are the ones launched
   set_kinds(p.get(), t);
   hipError_t e = hipGetDevice(&p->device);
   if (e == hipSuccess) e = upload_tables(p.get(), t, {});
-  if (e != hipSuccess)
-    return set_err(FA_E_HIP, "fa_plan_create_from_tiles: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return set_err(FA_E_HIP, "%s: %s", who, hipGetErrorString(e));
   *out = p.release();
   return FA_OK;
+}
+}  // namespace
+
+int fa_plan_create_from_tiles(const fa_tile_desc* tiles, int ntiles, int64_t f32_numel,
+                              int64_t i64_numel, int tile_elems, unsigned flags,
+                              fa_plan** out) {
+  return plan_from_tiles("fa_plan_create_from_tiles", tiles, ntiles, f32_numel, i64_numel,
+                         tile_elems, flags, FA_ELEM_F32, FA_ELEM_F32, out);
+}
+
+int fa_plan_create_from_tiles_elem(const fa_tile_desc* tiles, int ntiles, int64_t f32_numel,
+                                   int64_t i64_numel, int tile_elems, unsigned flags, int elem,
+                                   int out_elem, fa_plan** out) {
+  if (elem == FA_ELEM_F32 && out_elem == FA_ELEM_F32)
+    return fa_plan_create_from_tiles(tiles, ntiles, f32_numel, i64_numel, tile_elems, flags, out);
+  if (!out) return set_err(FA_E_INVAL, "fa_plan_create_from_tiles_elem: out is NULL");
+  *out = nullptr;
+  if (!((elem == FA_ELEM_F16 || elem == FA_ELEM_BF16) &&
+        (out_elem == elem || out_elem == FA_ELEM_F32)))
+    return set_err(FA_E_INVAL, "fa_plan_create_from_tiles_elem: out_elem must equal elem, or be "
+                               "FA_ELEM_F32 over FA_ELEM_F16 / FA_ELEM_BF16 clients (got elem %d, "
+                               "out_elem %d)", elem, out_elem);
+  return plan_from_tiles("fa_plan_create_from_tiles_elem", tiles, ntiles, f32_numel, i64_numel,
+                         tile_elems, flags, elem, out_elem, out);
 }
 
 int fa_plan_destroy(fa_plan* plan) {
@@ -1841,6 +1881,20 @@ int fa_read_probe_f32(const float* src, int64_t numel, float* out, int grid, voi
                        numel / 4, out);
   }
   HIP_TRY(hipGetLastError());
+  return FA_OK;
+}
+
+int fa_narrow_f32(const float* src, void* dst, int elem, int64_t numel, void* stream) {
+  if (elem != FA_ELEM_F16 && elem != FA_ELEM_BF16)
+    return set_err(FA_E_INVAL, "fa_narrow_f32: elem must be FA_ELEM_F16 or FA_ELEM_BF16 (got %d)",
+                   elem);
+  if (numel < 0) return set_err(FA_E_INVAL, "fa_narrow_f32: numel=%lld", (long long)numel);
+  if (numel == 0) return FA_OK;
+  if (!src || !dst) return set_err(FA_E_INVAL, "fa_narrow_f32: NULL pointer");
+  if (!aligned16(src) || !aligned16(dst))
+    return set_err(FA_E_INVAL, "fa_narrow_f32: src / dst not 16-B aligned");
+  const hipError_t e = fa_h16::narrow_range(src, dst, elem, numel, (hipStream_t)stream);
+  if (e != hipSuccess) return set_err(FA_E_HIP, "fa_narrow_f32: %s", hipGetErrorString(e));
   return FA_OK;
 }
 

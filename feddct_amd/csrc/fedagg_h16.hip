@@ -29,6 +29,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "common.h"
@@ -409,6 +410,46 @@ hipError_t bcast_narrow(const ReduceArgs& a, int n, int elem, int64_t f32_numel,
     launch_bg<FA_ELEM_F16>(a, grid, (uint32_t)fparts, groups, gsize, f32_numel, i64_numel, st);
   else
     launch_bg<FA_ELEM_BF16>(a, grid, (uint32_t)fparts, groups, gsize, f32_numel, i64_numel, st);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------- narrowing one range ----
+// fa_narrow_f32: a range of an fp32 bucket rounded into ONE 16-bit
+// destination (the chunk of a mixed host-resident round's result that goes
+// back over PCIe in the clients' type, pipeline.py).  A kernel of its own:
+// plain pointer arguments, no client table, no G-way store loop (the
+// broadcast above is not re-templated for it).  One workgroup per kTile
+// elements, two 16-B loads and one 16-B store per lane — the broadcast's
+// whole-part shape, the same narrow8 / narrow bits; the last workgroup also
+// narrows the numel % 8 trailing elements.  The result is read next by a
+// D2H copy, not by a kernel: plain stores.
+template <int EL>
+__global__ __launch_bounds__(kBlock) void narrow_range_kernel(const float* __restrict__ src,
+                                                              uint16_t* __restrict__ dst,
+                                                              int64_t numel) {
+  const int64_t nv = numel / kVec;                      // whole 8-element vectors
+  const int64_t vb = (int64_t)blockIdx.x * kBlock;      // the workgroup's first vector
+  const uint32_t t = threadIdx.x;
+  if (vb + t < nv) {
+    const float* s = src + kVec * vb;
+    const u4 r = narrow8<EL>(ldg4<false>(s, 2 * t), ldg4<false>(s, 2 * t + 1));
+    *((u4*)(dst + kVec * vb) + t) = r;
+  }
+  if (blockIdx.x == gridDim.x - 1 && (int64_t)t < numel - kVec * nv)
+    dst[kVec * nv + t] = (uint16_t)narrow<EL>(src[kVec * nv + t]);
+}
+
+hipError_t narrow_range(const float* src, void* dst, int elem, int64_t numel, hipStream_t st) {
+  if (numel <= 0) return hipSuccess;
+  if (elem != FA_ELEM_F16 && elem != FA_ELEM_BF16) return hipErrorInvalidValue;
+  const int64_t parts = std::max<int64_t>(1, (numel / kVec + kBlock - 1) / kBlock);
+  if (parts > (int64_t)INT32_MAX) return hipErrorInvalidValue;
+  if (elem == FA_ELEM_F16)
+    hipLaunchKernelGGL(narrow_range_kernel<FA_ELEM_F16>, dim3((uint32_t)parts), dim3(kBlock), 0,
+                       st, src, (uint16_t*)dst, numel);
+  else
+    hipLaunchKernelGGL(narrow_range_kernel<FA_ELEM_BF16>, dim3((uint32_t)parts), dim3(kBlock), 0,
+                       st, src, (uint16_t*)dst, numel);
   return hipGetLastError();
 }
 

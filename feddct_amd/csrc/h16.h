@@ -24,4 +24,8 @@ constexpr int kBcastGroup = 24;
 // copied into every int64 bucket; either count may be 0.
 hipError_t bcast_narrow(const fa_k::ReduceArgs& a, int n, int elem, int64_t f32_numel,
                         int64_t i64_numel, hipStream_t st);
+
+// src[0, numel) rounded to nearest-even into the one 16-bit bucket dst[0, numel)
+// (fa_narrow_f32): both 16-B aligned, any numel.
+hipError_t narrow_range(const float* src, void* dst, int elem, int64_t numel, hipStream_t st);
 }  // namespace fa_h16

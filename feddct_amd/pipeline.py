@@ -24,6 +24,17 @@ ways: ``fanout="host"`` (default) downloads each chunk of the result once
 and copies it into every target on the CPU (ATen's multi-threaded copy)
 while the GPU uploads the next chunks; ``fanout="dma"`` downloads it once
 per target (N D2H copies per chunk on stream B).
+
+A native 16-bit layout (layout.py ``native16``: host-resident
+``model.half()`` / ``model.bfloat16()`` federations) moves 2 B per element
+each way: the staging buckets hold the clients' dtype and the chunks are
+16-bit range plans.  With ``master=True`` (an fp32 master global) the chunks
+are mixed plans: the device result is fp32 and goes to the global's fp32 host
+bucket unrounded, and before a broadcast each chunk is also narrowed on the
+GPU (fa_narrow_f32) into a second, 16-bit device bucket from which the
+broadcast targets are fed — once into the first target, then fanned out on
+the CPU (``host``), or once per target (``dma``).  The tapers below were
+tuned on fp32 chunks and are not re-measured for 16-bit ones.
 """
 from __future__ import annotations
 
@@ -47,30 +58,41 @@ class HostPipeline:
     TAPER_NO_BCAST = (0.9375, 0.0625)
 
     def __init__(self, layout: BucketLayout, n: int, device: torch.device, nchunks: int = 0,
-                 tile_elems: int = 0, fanout: str = "host", fractions=None):
+                 tile_elems: int = 0, fanout: str = "host", fractions=None,
+                 master: bool = False):
         """``nchunks`` 0: the tapered cut (``fractions``, default TAPER); > 0:
-        that many even chunks."""
+        that many even chunks.  ``layout``: the clients' layout; ``master``:
+        a native 16-bit layout under an fp32 master global."""
         if fanout not in ("host", "dma"):
             raise ValueError(f"fanout must be 'host' or 'dma', not {fanout!r}")
+        if master and not layout.native16:
+            raise ValueError("master=True needs the clients' native 16-bit layout")
         self.layout = layout
         self.device = device
         self.fanout = fanout
+        self.master = bool(master)
+        self.elem = _lib.ELEM_OF_DTYPE[layout.float_dtype]
+        kw = dict(out_elem=_lib.FA_ELEM_F32) if master else {}
         with torch.cuda.device(device):
             if nchunks > 0:
-                self.ranges, self.plan64 = range_plans(layout, nchunks, tile_elems)
+                self.ranges, self.plan64 = range_plans(layout, nchunks, tile_elems, **kw)
                 self.ranges_nb = self.ranges
             else:
                 fr = tuple(fractions or self.TAPER)
                 self.ranges, self.plan64 = range_plans(layout, len(fr), tile_elems,
-                                                       fractions=fr)
+                                                       fractions=fr, **kw)
                 fr = tuple(fractions or self.TAPER_NO_BCAST)
-                self.ranges_nb = range_plans(layout, len(fr), tile_elems, fractions=fr)[0]
+                self.ranges_nb = range_plans(layout, len(fr), tile_elems, fractions=fr, **kw)[0]
             # the staged client buckets side by side in one slab (slab.py)
-            self.dev32 = [slab.carve(max(layout.f32_numel, 64), torch.float32, device)
+            self.dev32 = [slab.carve(max(layout.f32_numel, 64), layout.float_dtype, device)
                           for _ in range(n)]
             self.dev64 = [torch.empty(max(layout.i64_numel, 1), dtype=torch.int64,
                                       device=device) for _ in range(n)]
-            self.out32 = slab.carve(self.dev32[0].numel(), torch.float32, device)
+            self.out32 = slab.carve(self.dev32[0].numel(),
+                                    torch.float32 if master else layout.float_dtype, device)
+            # master: the result narrowed to the clients' dtype, chunk by chunk
+            self.out16 = (slab.carve(self.dev32[0].numel(), layout.float_dtype, device)
+                          if master else None)
             self.out64 = torch.zeros_like(self.dev64[0])
             self.s_in = torch.cuda.Stream(device)
             self.s_out = torch.cuda.Stream(device)
@@ -85,6 +107,9 @@ class HostPipeline:
         """One round.  ``host*`` are the clients' host buckets (slot order),
         ``out_host*`` the global's, ``bcast*`` extra host buckets that receive
         the result (the broadcast; they may be the clients' own buckets).
+        The floating buckets have the layout's dtype; under ``master``
+        ``out_host32`` is the global's fp32 bucket and takes the unrounded
+        mean, the ``bcast32`` targets its rounding to the clients' dtype.
         Returns after the result is in every host bucket."""
         fanout = fanout or self.fanout
         ranges = self.ranges if (bcast32 or bcast64) else self.ranges_nb
@@ -118,6 +143,10 @@ class HostPipeline:
                 ev_in.append(ev)
         stream = ctypes.c_void_p(compute.cuda_stream)
         dma = fanout == "dma"
+        # master: the broadcast's source is the narrowed device bucket; with
+        # the CPU fan-out it lands once, in the first target
+        narrow = self.master and len(bcast32) > 0
+        bsrc = self.out16 if narrow else self.out32
         ev_out = []
         for c, (lo, hi, plan) in enumerate(ranges):
             compute.wait_event(ev_in[c])
@@ -125,6 +154,10 @@ class HostPipeline:
                 _lib.check(_lib.lib.fa_reduce(plan.handle, self.a32, self.a64, n, w,
                                               self.out32.data_ptr(), self.out64.data_ptr(), 0,
                                               stream), "fa_reduce(chunk)")
+            if narrow and hi > lo:
+                _lib.check(_lib.lib.fa_narrow_f32(self.out32.data_ptr() + 4 * lo,
+                                                  self.out16.data_ptr() + 2 * lo, self.elem,
+                                                  hi - lo, stream), "fa_narrow_f32(chunk)")
             ev = torch.cuda.Event()
             ev.record(compute)
             self.s_out.wait_event(ev)
@@ -133,7 +166,9 @@ class HostPipeline:
                     out_host32[lo:hi].copy_(self.out32[lo:hi], non_blocking=True)
                     if dma:
                         for t in bcast32:
-                            t[lo:hi].copy_(self.out32[lo:hi], non_blocking=True)
+                            t[lo:hi].copy_(bsrc[lo:hi], non_blocking=True)
+                    elif narrow:
+                        bcast32[0][lo:hi].copy_(bsrc[lo:hi], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.s_out)
             ev_out.append(ev)
@@ -155,9 +190,10 @@ class HostPipeline:
             for (lo, hi, _), ev in zip(ranges, ev_out):
                 if hi > lo:
                     ev.synchronize()
-                    src = out_host32[lo:hi]
+                    first = bcast32[0] if narrow else out_host32
+                    src = first[lo:hi]
                     for t in bcast32:
-                        if t.data_ptr() != out_host32.data_ptr():
+                        if t.data_ptr() != first.data_ptr():
                             t[lo:hi].copy_(src)
         self.s_out.synchronize()
         if not dma:

@@ -150,9 +150,9 @@ int fa_plan_destroy(fa_plan *plan);
  *   FA_F_BCAST_ONLY copy the bucket's bytes flat and need a plan whose
  *   segments cover it (FA_PLAN_GAPS_ARE_PADDING, no gap of >= 128 elements)
  *   and an even f32_numel.  Refused with FA_E_INVAL on a 16-bit plan:
- *   FA_F_SUM_ONLY and fa_reduce_chain; fa_plan_create_order and
- *   fa_plan_create_from_tiles make fp32 plans only, as do the multi-GPU
- *   rounds of libfedagg_comm.so. */
+ *   FA_F_SUM_ONLY and fa_reduce_chain; fa_plan_create_order makes fp32 plans
+ *   only, as do the multi-GPU rounds of libfedagg_comm.so (tile subsets of a
+ *   16-bit table: fa_plan_create_from_tiles_elem). */
 #define FA_ELEM_F32 0
 #define FA_ELEM_F16 1
 #define FA_ELEM_BF16 2
@@ -221,6 +221,33 @@ int fa_plan_get_info(const fa_plan *plan, fa_plan_info *info);
 int fa_plan_create_from_tiles(const fa_tile_desc *tiles, int ntiles,
                               int64_t f32_numel, int64_t i64_numel,
                               int tile_elems, unsigned flags, fa_plan **out);
+/* ... of a table whose floating bucket holds `elem` elements, with the result
+ * in `out_elem` (FA_ELEM_*):
+ * (F32, F32): fa_plan_create_from_tiles exactly.
+ * elem F16 / BF16 with out_elem == elem (a 16-bit plan) or out_elem F32 (a
+ *   mixed plan): a subset of the table fa_plan_build_host_elem returns, in
+ *   ELEMENTS.  tile_elems: 2048 or 4096 (0 = the 16-bit default).  Vector
+ *   tiles need start % 8 == 0, count % 8 == 0 and count <= tile_elems; scalar
+ *   and int64 tiles as above; tiles must be disjoint; the caller's tiles are
+ *   the ones launched.  fa_reduce / fa_reduce_tab dispatch on the plan as on
+ *   a 16-bit / mixed segment plan (c32[i] the 16-bit buckets; out32 the 16-bit
+ *   bucket, or on a mixed plan the fp32 one of f32_numel floats).  A subset
+ *   does not cover its bucket, so FA_F_BCAST and FA_F_BCAST_ONLY are refused
+ *   with nothing written (the coverage rule above), as are FA_F_SUM_ONLY and
+ *   fa_reduce_chain.
+ * Every other pair is FA_E_INVAL.  *out is cleared first. */
+int fa_plan_create_from_tiles_elem(const fa_tile_desc *tiles, int ntiles,
+                                   int64_t f32_numel, int64_t i64_numel,
+                                   int tile_elems, unsigned flags, int elem,
+                                   int out_elem, fa_plan **out);
+/* src[0, numel) rounded to nearest-even into the 16-bit dst[0, numel) (elem
+ * FA_ELEM_F16 / FA_ELEM_BF16), as the mixed plan's broadcast rounds (a NaN is
+ * a NaN): one range of an fp32 result on its way out in the clients' type
+ * (the host-ingress pipeline's chunk).  Both pointers 16-B aligned, any
+ * numel; numel == 0 is FA_OK.  elem FA_ELEM_F32, a NULL or misaligned
+ * pointer: FA_E_INVAL, nothing launched. */
+int fa_narrow_f32(const float *src, void *dst, int elem, int64_t numel,
+                  void *stream);
 
 /* ---- launch shape by round count (r03) -------------------------------------
  * One workgroup per tile: T tiles over `slots` resident workgroups run
