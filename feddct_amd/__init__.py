@@ -17,9 +17,10 @@ def server_aggregate(global_model, client_models):
     return _sa(global_model, client_models)
 
 
-def set_summation_order(order: str, strict: bool = False) -> None:
+def set_summation_order(order: str, strict: bool = False, native16: bool = False) -> None:
     """"torch_cpu" (default) or "torch_gpu" (torch-ROCm's GPU mean on this
-    device, not the published NVIDIA runs' order): see
+    device, not the published NVIDIA runs' order); ``native16=True`` lets
+    fp16 / bf16 device rounds reduce natively under "torch_gpu": see
     aggregate.set_summation_order."""
     from .aggregate import set_summation_order as _s
-    _s(order, strict)
+    _s(order, strict, native16)

@@ -64,6 +64,7 @@ EXPORTS = [
     "fa_plan_create_elem", "fa_plan_build_host_elem", "fa_plan_elem",
     "fa_plan_create_elem_out", "fa_plan_out_elem",
     "fa_plan_create_from_tiles_elem", "fa_narrow_f32",
+    "fa_plan_create_order_elem", "fa_plan_build_order_host_elem",
 ]
 
 
@@ -148,6 +149,10 @@ def _load():
         "fa_torch_gpu_config": (_I, [_I, _I64, ctypes.POINTER(_I)]),
         "fa_plan_create_order": (_I, [_P, _I, _I64, _P, _I, _I64, _I, _I, ctypes.c_uint,
                                       ctypes.POINTER(_P)]),
+        "fa_plan_create_order_elem": (_I, [_P, _I, _I64, _P, _I, _I64, _I, _I, ctypes.c_uint, _I,
+                                           ctypes.POINTER(_P)]),
+        "fa_plan_build_order_host_elem": (_I, [_P, _I, _I64, _P, _I, _I64, _I, _I, ctypes.c_uint,
+                                               _I, _I, _P, _P, _I, _P, ctypes.POINTER(_I)]),
         "fa_reduce_chain": (_I, [_P, _P, _I, _P, ctypes.POINTER(FaChain), _P, ctypes.c_uint, _P]),
         "fa_norm_plan_create": (_I, [_P, _I, _I64, ctypes.POINTER(_P)]),
         "fa_norm_plan_destroy": (_I, [_P]),
@@ -218,6 +223,31 @@ def build_tiles_host(segs32, f32_numel, segs64=(), i64_numel=0, tile_elems=0,
     tiles = np.array([(arr[i].start, arr[i].count, arr[i].kind) for i in range(cap)],
                      np.int64).reshape(-1, 3)
     return {f: getattr(info, f) for f, _ in FaPlanInfo._fields_}, tiles
+
+
+def build_order_tiles_host(segs32, f32_numel, segs64=(), i64_numel=0, n=2,
+                           order=FA_ORDER_TORCH_GPU, flags=FA_PLAN_GAPS_ARE_PADDING,
+                           elem=FA_ELEM_F32, slots=0):
+    """The torch-GPU-order table of a layout for ``n`` clients, computed by
+    the library on the host (fa_plan_build_order_host_elem, no GPU): returns
+    (ndarray of (start, count, kind) in launch order, float32 ndarray of the
+    tiles' mean factors, the six launch-group bounds lo)."""
+    a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
+    a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
+    head = (a32, n32, int(f32_numel), a64, n64, int(i64_numel), int(n), int(order), flags,
+            int(elem), int(slots))
+    nt = _I()
+    check(lib.fa_plan_build_order_host_elem(*head, None, None, 0, None, ctypes.byref(nt)),
+          "fa_plan_build_order_host_elem")
+    cap = nt.value
+    arr = (FaTileDesc * max(1, cap))()
+    fac = (ctypes.c_float * max(1, cap))()
+    lo = (_I * 6)()
+    check(lib.fa_plan_build_order_host_elem(*head, arr, fac, cap, lo, ctypes.byref(nt)),
+          "fa_plan_build_order_host_elem")
+    tiles = np.array([(arr[i].start, arr[i].count, arr[i].kind) for i in range(cap)],
+                     np.int64).reshape(-1, 3)
+    return tiles, np.array(fac[:cap], np.float32), [int(x) for x in lo]
 
 
 def balance_host(vec_tiles, tile_elems=2048, nscalar=0, slots=768):
@@ -315,6 +345,26 @@ class Plan:
                                                  int(tile_elems), flags, self.elem, self.out_elem,
                                                  ctypes.byref(h)),
               "fa_plan_create_from_tiles_elem")
+        self.handle = h
+        info = FaPlanInfo()
+        check(lib.fa_plan_get_info(h, ctypes.byref(info)), "fa_plan_get_info")
+        self.info = {f: getattr(info, f) for f, _ in FaPlanInfo._fields_}
+        return self
+
+    @classmethod
+    def for_order(cls, segs32, f32_numel, segs64=(), i64_numel=0, n=0,
+                  elem=FA_ELEM_F32, flags=FA_PLAN_GAPS_ARE_PADDING, order=FA_ORDER_TORCH_GPU):
+        """A plan of ``order`` for ``n`` clients over a floating bucket of
+        ``elem`` elements (fa_plan_create_order_elem): with a 16-bit ``elem``
+        and the torch-GPU order, the native 16-bit plan of that order."""
+        self = cls.__new__(cls)
+        self.elem = self.out_elem = int(elem)
+        a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
+        a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
+        h = ctypes.c_void_p()
+        check(lib.fa_plan_create_order_elem(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
+                                            int(n), int(order), flags, int(elem),
+                                            ctypes.byref(h)), "fa_plan_create_order_elem")
         self.handle = h
         info = FaPlanInfo()
         check(lib.fa_plan_get_info(h, ctypes.byref(info)), "fa_plan_get_info")

@@ -218,10 +218,22 @@ class Engine:
         # every later layout / N from a caller who set the order for parity
         self.gpu_order_fallbacks: Dict[tuple, int] = {}
         self.strict_gpu_order = False
+        # set_summation_order(..., native16=True): under the torch-GPU order,
+        # all-16-bit device rounds bind the native 16-bit layout and reduce
+        # through fa_plan_create_order_elem's plan instead of being staged
+        self.native16_gpu_order = False
         self._fallback_round = False
         self._layouts: Dict[tuple, BucketLayout] = {}
         self._pipes: Dict[tuple, object] = {}
         self._round: Optional[_RoundBinding] = None
+
+    @property
+    def order_key(self) -> str:
+        """What a bound round is bound to: the summation order, and under the
+        torch-GPU order whether 16-bit rounds run natively."""
+        if self.order == "torch_gpu" and self.native16_gpu_order:
+            return "torch_gpu+native16"
+        return self.order
 
     # ------------------------------------------------------------ caches --
     GPU_PLAN_CACHE = 8
@@ -241,8 +253,13 @@ class Engine:
                 return self._gpu_plans[key]
             try:
                 with torch.cuda.device(device):
-                    p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
-                                  layout.i64_numel, order=_lib.FA_ORDER_TORCH_GPU, n=n)
+                    if layout.native16:   # (bound only with native16_gpu_order)
+                        p = _lib.Plan.for_order(layout.segs32, layout.f32_numel, layout.segs64,
+                                                layout.i64_numel, n=n,
+                                                elem=_lib.ELEM_OF_DTYPE[layout.float_dtype])
+                    else:
+                        p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
+                                      layout.i64_numel, order=_lib.FA_ORDER_TORCH_GPU, n=n)
             except _lib.FedaggError as e:
                 if "outside the restated" not in str(e):
                     raise
@@ -288,6 +305,12 @@ class Engine:
         buckets with per-call staging."""
         if self.order != "torch_cpu":
             return None, None
+        return self._device_round_dtypes(global_model, client_models)
+
+    def _device_round_dtypes(self, global_model, client_models):
+        """_round_dtypes' placement and dtype rules, the summation order not
+        looked at (round_layouts asks it for the torch-GPU order's native
+        16-bit rounds, set_summation_order(..., native16=True))."""
         gdts, cdts, devs = set(), set(), set()
         for i, m in enumerate((global_model, *client_models)):
             dts = cdts if i else gdts
@@ -374,6 +397,12 @@ class Engine:
         t = _first_tensor(client_models[0]) if len(client_models) else None
         if t is not None and t.device.type == "cpu":
             kind, h16 = self._host_round_dtypes(global_model, client_models)
+        elif self.order == "torch_gpu" and self.native16_gpu_order:
+            # the torch-GPU order reduces all-16-bit rounds natively; an fp32
+            # master over 16-bit clients stays staged there
+            kind, h16 = self._device_round_dtypes(global_model, client_models)
+            if kind != "native":
+                kind, h16 = None, None
         else:
             kind, h16 = self._round_dtypes(global_model, client_models)
         if kind == "mixed":
@@ -415,7 +444,7 @@ class Engine:
         (VERDICT r05 next 2).  r06: the native check reads cached TensorImpl
         fields (shim.cpp ViewKey) instead of unpacking every Python tensor."""
         rb = self._round
-        if rb is None or not rb.same_modules(global_model, client_models, self.order,
+        if rb is None or not rb.same_modules(global_model, client_models, self.order_key,
                                              weights is not None):
             return False
         return self._run_bound(rb, weights)
@@ -504,7 +533,8 @@ class Engine:
                 if fuse_bcast and _arena._fa_shim is not None and not self._fallback_round:
                     a32, a64 = self._ptr_arrays(cas)
                     self._round = _RoundBinding(self, global_model, client_models, ga, cas,
-                                                plan, a32, a64, self.order, weights is not None)
+                                                plan, a32, a64, self.order_key,
+                                                weights is not None)
             else:
                 o32, o64 = self._stage(layout, dev)
                 self._reduce_device(layout, o32, o64, cas, weights, fuse_bcast)
@@ -680,7 +710,7 @@ def server_aggregate_split(global_model_a, global_model_b, models_a, models_b):
     # the repeat call's fast path: the very objects of the last joint round
     # (no pair lookups: 25 of them cost cfg5's call ~10 us of host time)
     rb = e._round
-    if (rb is not None and rb.split_ids is not None and rb.current(e.order, False)
+    if (rb is not None and rb.split_ids is not None and rb.current(e.order_key, False)
             and _arena._fa_shim.src_match(rb.split_ids, global_model_a, global_model_b,
                                           models_a, models_b)
             and e._run_bound(rb)):
@@ -732,7 +762,7 @@ def aggregate_weighted(global_model, client_models, weights=None, sizes=None,
         engine().reduce_modules(global_model, list(client_models), w, broadcast)
 
 
-def set_summation_order(order: str, strict: bool = False) -> None:
+def set_summation_order(order: str, strict: bool = False, native16: bool = False) -> None:
     """Which torch order device-resident rounds reproduce bit for bit:
     ``"torch_cpu"`` (default: torch's CPU stack(...).mean(0), the reference's
     BASELINE config 1 and its device-independent definition) or
@@ -747,11 +777,22 @@ def set_summation_order(order: str, strict: bool = False) -> None:
     for each new (layout, N) and a count in ``engine().gpu_order_fallbacks``
     — or, with ``strict=True``, raises instead.  See INTEGRATION.md).
     Host-resident modules always take the CPU order, which is what the
-    reference computes for them."""
+    reference computes for them.
+
+    ``native16=True`` (opt-in; every call sets it, so a call without it
+    switches it off): under ``"torch_gpu"``, a round whose global and clients
+    sit on one GPU with every non-int64 key of the one 16-bit dtype
+    (``model.half()`` / ``model.bfloat16()``) binds the native 16-bit layout
+    and reduces from the 16-bit buckets in the torch-GPU order
+    (fa_plan_create_order_elem) instead of being staged through fp32 buckets
+    per call; weighted rounds, N < 2 and rounds outside the restatement take
+    the CPU order on the same 16-bit buckets, under the rules above.  An fp32
+    master global over 16-bit clients stays staged.  DESIGN.md §4.12."""
     if order not in ORDERS:
         raise ValueError(f"order must be one of {sorted(ORDERS)}, not {order!r}")
     engine().order = order
     engine().strict_gpu_order = bool(strict)
+    engine().native16_gpu_order = bool(native16)
 
 
 def summation_order() -> str:

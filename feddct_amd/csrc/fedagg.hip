@@ -54,6 +54,7 @@ int fa::set_err(int code, const char* fmt, ...) {
 
 #include "reduce_impl.h"
 #include "h16.h"
+#include "tgpu16.h"
 
 // the reduce kernels' launchers are instantiated in the fedagg_k*.hip units
 FA_K_UNITS(extern)
@@ -1254,6 +1255,73 @@ int fa_plan_create_order(const fa_seg* seg32, int nseg32, int64_t f32_numel, con
 }
 
 namespace {
+// Resident workgroups of the 16-bit S = 1 group's kernel (fedagg_tgpu16.hip)
+// on `dev`, queried once per process and element type (0: unknown).
+int tgpu16_slots(int dev, int elem) {
+  static std::mutex mu;
+  static std::map<int, int> cache;
+  std::lock_guard<std::mutex> lk(mu);
+  const int key = dev * 4 + elem;
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  int cus = 0;
+  const int occ = fa_tgpu16::occupancy_s1(elem);
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 0;
+  return cache[key] = occ > 0 && cus > 0 ? occ * cus : 0;
+}
+}  // namespace
+
+int fa_plan_create_order_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                              const fa_seg* seg64, int nseg64, int64_t i64_numel, int n, int order,
+                              unsigned flags, int elem, fa_plan** out) {
+  if (elem == FA_ELEM_F32)
+    return fa_plan_create_order(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order,
+                                flags, out);
+  if (order == FA_ORDER_TORCH_CPU)
+    return fa_plan_create_elem(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags, elem,
+                               out);
+  const char* who = "fa_plan_create_order_elem";
+  int rc = fa_host::check_flags(who, flags);
+  if (rc) return rc;
+  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
+  *out = nullptr;
+  // the planner's one device input: the S = 1 launch's resident workgroups
+  // (asked only for an element type that has a kernel; the checks below
+  // refuse every other)
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  const bool known = elem == FA_ELEM_F16 || elem == FA_ELEM_BF16;
+  const int slots =
+      e == hipSuccess && known && !(flags & FA_PLAN_TUNE_NO_BALANCE) ? tgpu16_slots(dev, elem) : 0;
+  fa_host::Layout l;
+  fa_host::TgpuTables t;
+  rc = fa_host::plan_order_elem(who, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order,
+                                flags, elem, slots, &l, &t);
+  if (rc) return rc;
+  PlanPtr p(new fa_plan());
+  for (int g = 0; g < 6; ++g) p->tg_lo[g] = t.lo[g];
+  p->info = l.info;
+  p->info.ntiles = (int32_t)t.tiles.size();
+  p->info.ntiles_tail = (int32_t)t.tiles.size();
+  p->flags = flags;
+  p->elem = p->out_elem = elem;
+  p->vec_u = 1;
+  p->flat_bcast = fa_host::flat_bcast_ok(flags, l, elem, elem);
+  p->order = FA_ORDER_TORCH_GPU;
+  p->order_n = n;
+  set_kinds(p.get(), t.tiles);
+  p->device = dev;
+  // (no LDS reservation on the S = 2 launch: tgpu_s2_lds was measured on the
+  // fp32 instance only)
+  if (e == hipSuccess) e = upload(&p->d_tiles, t.tiles);
+  if (e == hipSuccess) e = upload(&p->d_fac, t.fac);
+  if (e != hipSuccess) return set_err(FA_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  *out = p.release();
+  return FA_OK;
+}
+
+namespace {
 // One body behind fa_plan_create_from_tiles and ..._from_tiles_elem (`who`,
 // in the messages).  A 16-bit or mixed subset plan is cut from
 // fa_plan_build_host_elem's table: vectors of 8 elements, tiles of 2048 or
@@ -1569,6 +1637,27 @@ hipError_t run_tgpu(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipSt
   return e;
 }
 
+// a 16-bit torch-GPU-order plan (fa_plan_create_order_elem): one launch of
+// fedagg_tgpu16.hip's kernels per row-split group, then the flat byte copy
+// of the result bucket (fa_reduce_tab has refused a plan without coverage)
+hipError_t run_tgpu16(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  for (int g = 0; g < 5 && e == hipSuccess; ++g) {
+    const int lo = plan->tg_lo[g], cnt = plan->tg_lo[g + 1] - lo;
+    if (cnt == 0) continue;
+    a.tiles = plan->d_tiles + lo;
+    a.tfac = plan->d_fac + lo;
+    a.ntiles = cnt;
+    e = fa_tgpu16::launch(a, g, cnt, plan->elem, st);
+  }
+  if (e == hipSuccess && bcast && plan->tg_lo[5] > 0) {
+    a.tiles = plan->d_tiles;
+    a.ntiles = plan->tg_lo[5];
+    e = launch_bcast(plan, a, n, a.ntiles, st);
+  }
+  return e;
+}
+
 // the 16-bit kernels (fedagg_h16.hip) over the plan's one table, then the
 // broadcast's flat copy of the result bucket
 hipError_t run_h16(const fa_plan* plan, ReduceArgs& a, int n, bool weighted, bool bcast,
@@ -1664,6 +1753,9 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
   if (bcast_only) {
     what = "broadcast launch";
     e = run_bcast_only(plan, a, n, st);
+  } else if (tgpu && h16) {
+    what = "16-bit torch-GPU-order launch";
+    e = run_tgpu16(plan, a, n, bcast, st);
   } else if (tgpu) {
     what = "torch-GPU-order launch";
     e = run_tgpu(plan, a, n, bcast, st);

@@ -572,6 +572,25 @@ void tgpu_split_tail(std::vector<Tile>* t, std::vector<float>* fac, int lo[6], i
 
 int plan_tgpu(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, int n,
               unsigned flags, int slots_s1, TgpuTables* out) {
+  return plan_tgpu(s32, s64, n, flags, slots_s1, out, 4);
+}
+
+// valign: elements per 16-B vector of the floating bucket.  4: the fp32 table
+// above.  8 (fa_h16::kVec): a 16-bit bucket — vector tiles start and end on
+// 8-element boundaries and hold up to fa_h16::kTile = 2048 elements at every
+// row split (one 16-B load per lane per row); the (8 - offset % 8) % 8
+// element head and the <= 7 element tail go to scalar tiles of the same S
+// and factor.  Everything else — S and factor per key, runs across key
+// boundaries, packed one-element keys, the grouping, the riders, lo[] — is
+// the one rule.
+int plan_tgpu(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, int n,
+              unsigned flags, int slots_s1, TgpuTables* out, int valign) {
+  if (valign != 4 && valign != fa_h16::kVec)
+    return set_err(FA_E_INVAL, "torch-GPU order planner: vector alignment %d", valign);
+  const bool h16 = valign == fa_h16::kVec;
+  // elements of a wide (S <= 2) and of a vector (S >= 4) tile
+  const int64_t te_w = h16 ? fa_h16::kTile : 8 * kBlock;
+  const int64_t te_v = h16 ? fa_h16::kTile : 4 * kBlock;
   std::vector<Tile>& t = out->tiles;
   std::vector<float>& fac = out->fac;
   t.clear();
@@ -594,7 +613,7 @@ int plan_tgpu(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, in
   float run_f = 0.f;
   auto flush = [&]() {
     if (run_s < 0) return;
-    const int64_t te = run_ls <= 1 ? 8 * kBlock : 4 * kBlock;
+    const int64_t te = run_ls <= 1 ? te_w : te_v;
     const int kind = (run_ls <= 1 ? K_F32_TGPU_W : K_F32_TGPU_V) | (run_ls << 8);
     for (int64_t c = run_s; c < run_e; c += te) {
       t.push_back(Tile{c, (int32_t)std::min<int64_t>(te, run_e - c), kind});
@@ -641,8 +660,8 @@ int plan_tgpu(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, in
       }
       // fp32: the 16-B aligned body in 4-element-per-lane tiles, the <= 3
       // element head and tail one element per lane (same order, same factor)
-      const int64_t head = std::min<int64_t>((4 - g.offset % 4) % 4, g.numel);
-      const int64_t body = (g.numel - head) / 4 * 4;
+      const int64_t head = std::min<int64_t>((valign - g.offset % valign) % valign, g.numel);
+      const int64_t body = (g.numel - head) / valign * valign;
       // S = 1: 2048-element tiles, the default reduce's load shape (r02:
       // 151.9 us on cfg2 with the 1024-element form); S = 2 too since r05
       // (tgpu_wide_loop); a key whose body is not 16-B aligned keeps its own
@@ -667,7 +686,7 @@ int plan_tgpu(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, in
       }
       flush();
       scalar(0, head);
-      const int64_t te = wide ? 8 * kBlock : 4 * kBlock;
+      const int64_t te = wide ? te_w : te_v;
       for (int64_t c = head; c < head + body; c += te) {
         t.push_back(Tile{g.offset + c, (int32_t)std::min<int64_t>(te, head + body - c),
                          (wide ? K_F32_TGPU_W : K_F32_TGPU_V) | (ls << 8)});
@@ -728,6 +747,23 @@ int plan_tgpu(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, in
   // (profiles/r06_ab_lib_tgpu_runs.jsonl, variant "nobal"): not applied
   if (!(flags & FA_PLAN_TUNE_NO_BALANCE)) tgpu_split_tail(&t, &fac, lo, 0, slots_s1);
   return FA_OK;
+}
+
+int plan_order_elem(const char* who, const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                    const fa_seg* seg64, int nseg64, int64_t i64_numel, int n, int order,
+                    unsigned flags, int elem, int slots_s1, Layout* l, TgpuTables* out) {
+  int rc = check_flags(who, flags);
+  if (rc) return rc;
+  if (order != FA_ORDER_TORCH_GPU) return set_err(FA_E_INVAL, "%s: order %d", who, order);
+  if (n < 2 || n > FA_MAX_CLIENTS)
+    return set_err(FA_E_RANGE, "%s: n=%d outside 2..%d", who, n, FA_MAX_CLIENTS);
+  // (tile_elems 0: the element type's own width; a 16-bit table is cut in
+  // fa_h16::kTile-element tiles whatever it says)
+  rc = parse_layout(who, "", kCheckSizes | kCheckTile, seg32, nseg32, f32_numel, seg64, nseg64,
+                    i64_numel, 0, flags, elem, l);
+  if (rc) return rc;
+  return plan_tgpu(l->s32, l->s64, n, flags, (flags & FA_PLAN_TUNE_NO_BALANCE) ? 0 : slots_s1,
+                   out, l->valign);
 }
 
 // -------------------------------------------------------- launch rules --
@@ -851,6 +887,33 @@ int fa_plan_build_host_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel,
                               flags, tiles, cap, info);
   return plan_build_host("fa_plan_build_host_elem", seg32, nseg32, f32_numel, seg64, nseg64,
                          i64_numel, tile_elems, flags, elem, tiles, cap, info);
+}
+
+int fa_plan_build_order_host_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                                  const fa_seg* seg64, int nseg64, int64_t i64_numel, int n,
+                                  int order, unsigned flags, int elem, int slots,
+                                  fa_tile_desc* tiles, float* factors, int cap, int* lo,
+                                  int* ntiles) {
+  const char* who = "fa_plan_build_order_host_elem";
+  if (!ntiles) return set_err(FA_E_INVAL, "%s: ntiles is NULL", who);
+  if (slots < 0 || cap < 0) return set_err(FA_E_INVAL, "%s: bad arguments", who);
+  fa_host::Layout l;
+  fa_host::TgpuTables t;
+  const int rc = fa_host::plan_order_elem(who, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel,
+                                          n, order, flags, elem, slots, &l, &t);
+  if (rc) return rc;
+  *ntiles = (int)t.tiles.size();
+  if (lo)
+    for (int g = 0; g < 6; ++g) lo[g] = t.lo[g];
+  if (tiles || factors) {
+    if (cap < (int)t.tiles.size())
+      return set_err(FA_E_RANGE, "%s: %d tiles, capacity %d", who, (int)t.tiles.size(), cap);
+    for (size_t i = 0; i < t.tiles.size(); ++i) {
+      if (tiles) tiles[i] = fa_tile_desc{t.tiles[i].start, t.tiles[i].count, t.tiles[i].kind};
+      if (factors) factors[i] = t.fac[i];
+    }
+  }
+  return FA_OK;
 }
 
 int fa_plan_balance_host(const fa_tile_desc* vec, int nvec, int tile_elems, int nscalar,

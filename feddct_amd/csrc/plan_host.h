@@ -85,6 +85,17 @@ struct TgpuTables {
 };
 int plan_tgpu(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, int n,
               unsigned flags, int slots_s1, TgpuTables* out);
+// The same for a floating bucket of `valign` elements per 16-B vector: 4 is
+// the table above; 8 cuts a 16-bit bucket's (fa_plan_create_order_elem).
+int plan_tgpu(const std::vector<fa_seg>& s32, const std::vector<fa_seg>& s64, int n,
+              unsigned flags, int slots_s1, TgpuTables* out, int valign);
+// One body behind fa_plan_create_order_elem's 16-bit arm and
+// fa_plan_build_order_host_elem: the argument checks of the two parents
+// (flags, order, n, elem, segments) in their order and the table of a
+// torch-GPU-order plan over a bucket of `elem` elements.
+int plan_order_elem(const char* who, const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                    const fa_seg* seg64, int nseg64, int64_t i64_numel, int n, int order,
+                    unsigned flags, int elem, int slots_s1, Layout* l, TgpuTables* out);
 
 // -------------------------------------------------------- launch rules --
 // What a launch decision reads of a default-order plan.

@@ -151,7 +151,8 @@ int fa_plan_destroy(fa_plan *plan);
  *   segments cover it (FA_PLAN_GAPS_ARE_PADDING, no gap of >= 128 elements)
  *   and an even f32_numel.  Refused with FA_E_INVAL on a 16-bit plan:
  *   FA_F_SUM_ONLY and fa_reduce_chain; fa_plan_create_order makes fp32 plans
- *   only, as do the multi-GPU rounds of libfedagg_comm.so (tile subsets of a
+ *   only (the torch-GPU order over a 16-bit bucket:
+ *   fa_plan_create_order_elem), as do the multi-GPU rounds of libfedagg_comm.so (tile subsets of a
  *   16-bit table: fa_plan_create_from_tiles_elem). */
 #define FA_ELEM_F32 0
 #define FA_ELEM_F16 1
@@ -302,6 +303,43 @@ int fa_torch_gpu_config(int n, int64_t m, int *stride);
 int fa_plan_create_order(const fa_seg *seg32, int nseg32, int64_t f32_numel,
                          const fa_seg *seg64, int nseg64, int64_t i64_numel,
                          int n, int order, unsigned flags, fa_plan **out);
+/* ... over a floating bucket of `elem` elements (FA_ELEM_*):
+ * elem FA_ELEM_F32: fa_plan_create_order exactly.
+ * order FA_ORDER_TORCH_CPU: fa_plan_create_elem exactly (tile_elems 0).
+ * elem FA_ELEM_F16 / FA_ELEM_BF16 with FA_ORDER_TORCH_GPU: the reference's
+ *   stack([c[k].float() ...], 0).mean(0) on device tensors of 16-bit clients,
+ *   copy_-ed into the 16-bit key.  Every value is widened exactly; the stacked
+ *   tensor is fp32, so S, the order and the factor are those of the fp32 plan
+ *   per key (fa_torch_gpu_config(n, M) unchanged); the fp32 result is rounded
+ *   to nearest-even into the 16-bit type (a NaN is a NaN).  Offsets, counts
+ *   and f32_numel are in 16-bit ELEMENTS; vector tiles start and end on 16-B
+ *   boundaries (8 elements) and hold up to 2048 elements.  Result type ==
+ *   elem (no mixed form).  The argument checks and messages are the two
+ *   parents' (FA_E_RANGE for n outside 2..FA_MAX_CLIENTS and for a key
+ *   "outside the restated configurations").  fa_reduce / fa_reduce_tab on
+ *   such a plan refuse with FA_E_INVAL, before any launch or allocation and
+ *   with nothing written: weights, n != the plan's n, FA_F_SUM_ONLY, and
+ *   FA_F_BCAST / FA_F_BCAST_ONLY without flat coverage (the 16-bit rule
+ *   above); fa_reduce_chain refuses it as every 16-bit plan. */
+int fa_plan_create_order_elem(const fa_seg *seg32, int nseg32,
+                              int64_t f32_numel, const fa_seg *seg64,
+                              int nseg64, int64_t i64_numel, int n, int order,
+                              unsigned flags, int elem, fa_plan **out);
+/* Host-only table of that plan (no device, no allocation; FA_ELEM_F32: the
+ * fp32 torch-GPU-order table), for tests and inspection: the tiles in launch
+ * order (kind: the tile kind, log2 S in bits 8-15, bit 16 the input-vectorised
+ * lane form), each tile's mean factor, and the launch groups lo[g]..lo[g+1]
+ * by row split S = 1 << g.  `slots`: the resident workgroups of the S = 1
+ * group's kernel the table is cut for (0: unknown).  order must be
+ * FA_ORDER_TORCH_GPU.  *ntiles is always filled; tiles / factors (cap entries
+ * each) and lo[6] may be NULL. */
+int fa_plan_build_order_host_elem(const fa_seg *seg32, int nseg32,
+                                  int64_t f32_numel, const fa_seg *seg64,
+                                  int nseg64, int64_t i64_numel, int n,
+                                  int order, unsigned flags, int elem,
+                                  int slots, fa_tile_desc *tiles,
+                                  float *factors, int cap, int *lo,
+                                  int *ntiles);
 
 /* The hot path: every key of N client buckets -> global bucket, one launch
  * (FA_F_BCAST: plus one broadcast launch — over the same tiles, or the flat
