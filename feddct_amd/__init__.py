@@ -17,10 +17,12 @@ def server_aggregate(global_model, client_models):
     return _sa(global_model, client_models)
 
 
-def set_summation_order(order: str, strict: bool = False, native16: bool = False) -> None:
+def set_summation_order(order: str, strict: bool = False, native16: bool = False,
+                        native16_master: bool = False) -> None:
     """"torch_cpu" (default) or "torch_gpu" (torch-ROCm's GPU mean on this
     device, not the published NVIDIA runs' order); ``native16=True`` lets
-    fp16 / bf16 device rounds reduce natively under "torch_gpu": see
-    aggregate.set_summation_order."""
+    fp16 / bf16 device rounds reduce natively under "torch_gpu", and
+    ``native16_master=True`` with it those of an fp32 master global over
+    fp16 / bf16 clients: see aggregate.set_summation_order."""
     from .aggregate import set_summation_order as _s
-    _s(order, strict, native16)
+    _s(order, strict, native16, native16_master)

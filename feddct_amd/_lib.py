@@ -65,6 +65,7 @@ EXPORTS = [
     "fa_plan_create_elem_out", "fa_plan_out_elem",
     "fa_plan_create_from_tiles_elem", "fa_narrow_f32",
     "fa_plan_create_order_elem", "fa_plan_build_order_host_elem",
+    "fa_plan_create_order_elem_out",
 ]
 
 
@@ -151,6 +152,8 @@ def _load():
                                       ctypes.POINTER(_P)]),
         "fa_plan_create_order_elem": (_I, [_P, _I, _I64, _P, _I, _I64, _I, _I, ctypes.c_uint, _I,
                                            ctypes.POINTER(_P)]),
+        "fa_plan_create_order_elem_out": (_I, [_P, _I, _I64, _P, _I, _I64, _I, _I, ctypes.c_uint,
+                                               _I, _I, ctypes.POINTER(_P)]),
         "fa_plan_build_order_host_elem": (_I, [_P, _I, _I64, _P, _I, _I64, _I, _I, ctypes.c_uint,
                                                _I, _I, _P, _P, _I, _P, ctypes.POINTER(_I)]),
         "fa_reduce_chain": (_I, [_P, _P, _I, _P, ctypes.POINTER(FaChain), _P, ctypes.c_uint, _P]),
@@ -353,18 +356,30 @@ class Plan:
 
     @classmethod
     def for_order(cls, segs32, f32_numel, segs64=(), i64_numel=0, n=0,
-                  elem=FA_ELEM_F32, flags=FA_PLAN_GAPS_ARE_PADDING, order=FA_ORDER_TORCH_GPU):
+                  elem=FA_ELEM_F32, flags=FA_PLAN_GAPS_ARE_PADDING, order=FA_ORDER_TORCH_GPU,
+                  out_elem=None):
         """A plan of ``order`` for ``n`` clients over a floating bucket of
         ``elem`` elements (fa_plan_create_order_elem): with a 16-bit ``elem``
-        and the torch-GPU order, the native 16-bit plan of that order."""
+        and the torch-GPU order, the native 16-bit plan of that order.
+        ``out_elem``: the result bucket's element type
+        (fa_plan_create_order_elem_out): FA_ELEM_F32 over 16-bit clients is
+        the plan of an fp32 master global in that order."""
         self = cls.__new__(cls)
-        self.elem = self.out_elem = int(elem)
+        self.elem = int(elem)
+        self.out_elem = self.elem if out_elem is None else int(out_elem)
         a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
         a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
         h = ctypes.c_void_p()
-        check(lib.fa_plan_create_order_elem(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
-                                            int(n), int(order), flags, int(elem),
-                                            ctypes.byref(h)), "fa_plan_create_order_elem")
+        if out_elem is None:
+            check(lib.fa_plan_create_order_elem(a32, n32, int(f32_numel), a64, n64,
+                                                int(i64_numel), int(n), int(order), flags,
+                                                int(elem), ctypes.byref(h)),
+                  "fa_plan_create_order_elem")
+        else:
+            check(lib.fa_plan_create_order_elem_out(a32, n32, int(f32_numel), a64, n64,
+                                                    int(i64_numel), int(n), int(order), flags,
+                                                    int(elem), int(out_elem), ctypes.byref(h)),
+                  "fa_plan_create_order_elem_out")
         self.handle = h
         info = FaPlanInfo()
         check(lib.fa_plan_get_info(h, ctypes.byref(info)), "fa_plan_get_info")

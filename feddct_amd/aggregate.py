@@ -222,6 +222,9 @@ class Engine:
         # all-16-bit device rounds bind the native 16-bit layout and reduce
         # through fa_plan_create_order_elem's plan instead of being staged
         self.native16_gpu_order = False
+        # ... native16_master=True: an fp32 master global over 16-bit clients
+        # too (fa_plan_create_order_elem_out) instead of being staged
+        self.native16_master_gpu_order = False
         self._fallback_round = False
         self._layouts: Dict[tuple, BucketLayout] = {}
         self._pipes: Dict[tuple, object] = {}
@@ -230,8 +233,11 @@ class Engine:
     @property
     def order_key(self) -> str:
         """What a bound round is bound to: the summation order, and under the
-        torch-GPU order whether 16-bit rounds run natively."""
+        torch-GPU order whether 16-bit rounds run natively, and whether those
+        under an fp32 master global do."""
         if self.order == "torch_gpu" and self.native16_gpu_order:
+            if self.native16_master_gpu_order:
+                return "torch_gpu+native16+master"
             return "torch_gpu+native16"
         return self.order
 
@@ -245,9 +251,10 @@ class Engine:
         some key across blocks there (outside the restated configurations,
         fa_torch_gpu_config).  ``master``: the mixed plan of a native 16-bit
         client layout under an fp32 master global (fp32 result bucket,
-        fa_plan_create_elem_out)."""
+        fa_plan_create_elem_out; under the torch-GPU order
+        fa_plan_create_order_elem_out)."""
         if order == "torch_gpu":
-            key = (layout.signature, device.index, n)
+            key = (layout.signature, device.index, n) + (("<master>",) if master else ())
             if key in self._gpu_plans:
                 self._gpu_plans.move_to_end(key)
                 return self._gpu_plans[key]
@@ -256,7 +263,8 @@ class Engine:
                     if layout.native16:   # (bound only with native16_gpu_order)
                         p = _lib.Plan.for_order(layout.segs32, layout.f32_numel, layout.segs64,
                                                 layout.i64_numel, n=n,
-                                                elem=_lib.ELEM_OF_DTYPE[layout.float_dtype])
+                                                elem=_lib.ELEM_OF_DTYPE[layout.float_dtype],
+                                                out_elem=_lib.FA_ELEM_F32 if master else None)
                     else:
                         p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
                                       layout.i64_numel, order=_lib.FA_ORDER_TORCH_GPU, n=n)
@@ -399,9 +407,10 @@ class Engine:
             kind, h16 = self._host_round_dtypes(global_model, client_models)
         elif self.order == "torch_gpu" and self.native16_gpu_order:
             # the torch-GPU order reduces all-16-bit rounds natively; an fp32
-            # master over 16-bit clients stays staged there
+            # master over 16-bit clients stays staged there unless
+            # native16_master asks for it too
             kind, h16 = self._device_round_dtypes(global_model, client_models)
-            if kind != "native":
+            if kind != "native" and not (kind == "mixed" and self.native16_master_gpu_order):
                 kind, h16 = None, None
         else:
             kind, h16 = self._round_dtypes(global_model, client_models)
@@ -608,8 +617,9 @@ class Engine:
         order = self.order
         if order == "torch_gpu" and (weights is not None or n < 2):
             order = "torch_cpu"   # (the GPU order is torch's unweighted mean, N >= 2)
-        # master: a mixed round (torch's CPU order by definition): `layout` is
-        # the clients' 16-bit one, out32 the global's fp32 bucket
+        # master: a mixed round (torch's CPU order, or with native16_master
+        # the torch-GPU one): `layout` is the clients' 16-bit one, out32 the
+        # global's fp32 bucket
         plan = self.plan(layout, dev, n, order, master)
         if plan is None:   # torch would split a key across blocks at this N
             msg = (f"feddct_amd: torch-GPU summation order is not restated for N={n} on "
@@ -622,7 +632,7 @@ class Engine:
             if seen == 0:
                 warnings.warn(msg + "; rounds of this layout at this N use torch's CPU order",
                               RuntimeWarning, stacklevel=3)
-            plan = self.plan(layout, dev, n, "torch_cpu")
+            plan = self.plan(layout, dev, n, "torch_cpu", master)
             self._fallback_round = True
         flags = _lib.FA_F_BCAST if fuse else 0
         a32, a64 = self._ptr_arrays(cas)
@@ -762,7 +772,8 @@ def aggregate_weighted(global_model, client_models, weights=None, sizes=None,
         engine().reduce_modules(global_model, list(client_models), w, broadcast)
 
 
-def set_summation_order(order: str, strict: bool = False, native16: bool = False) -> None:
+def set_summation_order(order: str, strict: bool = False, native16: bool = False,
+                        native16_master: bool = False) -> None:
     """Which torch order device-resident rounds reproduce bit for bit:
     ``"torch_cpu"`` (default: torch's CPU stack(...).mean(0), the reference's
     BASELINE config 1 and its device-independent definition) or
@@ -787,12 +798,25 @@ def set_summation_order(order: str, strict: bool = False, native16: bool = False
     (fa_plan_create_order_elem) instead of being staged through fp32 buckets
     per call; weighted rounds, N < 2 and rounds outside the restatement take
     the CPU order on the same 16-bit buckets, under the rules above.  An fp32
-    master global over 16-bit clients stays staged.  DESIGN.md §4.12."""
+    master global over 16-bit clients stays staged.  DESIGN.md §4.12.
+
+    ``native16_master=True`` (opt-in, with ``native16=True`` only —
+    ``ValueError`` otherwise; every call sets it too): under ``"torch_gpu"``,
+    a round of an fp32 master global over such 16-bit clients binds the master
+    layout and the clients' native 16-bit layout (zero-copy, as under the CPU
+    order) and reduces in the torch-GPU order into the global's fp32 bucket,
+    unrounded; the clients get its rounding to nearest-even
+    (fa_plan_create_order_elem_out).  Weighted rounds, N < 2 and rounds
+    outside the restatement take the CPU order's mixed plan on the same
+    buckets, under the rules above.  DESIGN.md §4.13."""
     if order not in ORDERS:
         raise ValueError(f"order must be one of {sorted(ORDERS)}, not {order!r}")
+    if native16_master and not native16:
+        raise ValueError("native16_master=True needs native16=True")
     engine().order = order
     engine().strict_gpu_order = bool(strict)
     engine().native16_gpu_order = bool(native16)
+    engine().native16_master_gpu_order = bool(native16_master)
 
 
 def summation_order() -> str:

@@ -1256,19 +1256,69 @@ int fa_plan_create_order(const fa_seg* seg32, int nseg32, int64_t f32_numel, con
 
 namespace {
 // Resident workgroups of the 16-bit S = 1 group's kernel (fedagg_tgpu16.hip)
-// on `dev`, queried once per process and element type (0: unknown).
-int tgpu16_slots(int dev, int elem) {
+// on `dev`, queried once per process, element type and store width (0:
+// unknown).
+int tgpu16_slots(int dev, int elem, bool wide) {
   static std::mutex mu;
   static std::map<int, int> cache;
   std::lock_guard<std::mutex> lk(mu);
-  const int key = dev * 4 + elem;
+  const int key = (dev * 4 + elem) * 2 + wide;
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   int cus = 0;
-  const int occ = fa_tgpu16::occupancy_s1(elem);
+  const int occ = fa_tgpu16::occupancy_s1(elem, wide);
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     cus = 0;
   return cache[key] = occ > 0 && cus > 0 ? occ * cus : 0;
+}
+
+// One body behind the torch-GPU-order arms of fa_plan_create_order_elem and
+// fa_plan_create_order_elem_out (`who`, in the messages): the table
+// fa_plan_build_order_host_elem returns for the clients' 16-bit type, with a
+// result bucket of that type or (out_elem FA_ELEM_F32) an fp32 one at the
+// same element offsets.
+int order_elem_plan(const char* who, const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                    const fa_seg* seg64, int nseg64, int64_t i64_numel, int n, int order,
+                    unsigned flags, int elem, int out_elem, fa_plan** out) {
+  int rc = fa_host::check_flags(who, flags);
+  if (rc) return rc;
+  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
+  *out = nullptr;
+  // the planner's one device input: the S = 1 launch's resident workgroups
+  // (asked only for an element type that has a kernel; the checks below
+  // refuse every other)
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  const bool known = elem == FA_ELEM_F16 || elem == FA_ELEM_BF16;
+  const int slots = e == hipSuccess && known && !(flags & FA_PLAN_TUNE_NO_BALANCE)
+                        ? tgpu16_slots(dev, elem, out_elem != elem)
+                        : 0;
+  fa_host::Layout l;
+  fa_host::TgpuTables t;
+  rc = fa_host::plan_order_elem(who, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order,
+                                flags, elem, slots, &l, &t);
+  if (rc) return rc;
+  PlanPtr p(new fa_plan());
+  for (int g = 0; g < 6; ++g) p->tg_lo[g] = t.lo[g];
+  p->info = l.info;
+  p->info.ntiles = (int32_t)t.tiles.size();
+  p->info.ntiles_tail = (int32_t)t.tiles.size();
+  p->flags = flags;
+  p->elem = elem;
+  p->out_elem = out_elem;
+  p->vec_u = 1;
+  p->flat_bcast = fa_host::flat_bcast_ok(flags, l, elem, out_elem);
+  p->order = FA_ORDER_TORCH_GPU;
+  p->order_n = n;
+  set_kinds(p.get(), t.tiles);
+  p->device = dev;
+  // (no LDS reservation on the S = 2 launch: tgpu_s2_lds was measured on the
+  // fp32 instance only)
+  if (e == hipSuccess) e = upload(&p->d_tiles, t.tiles);
+  if (e == hipSuccess) e = upload(&p->d_fac, t.fac);
+  if (e != hipSuccess) return set_err(FA_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  *out = p.release();
+  return FA_OK;
 }
 }  // namespace
 
@@ -1281,44 +1331,29 @@ int fa_plan_create_order_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel
   if (order == FA_ORDER_TORCH_CPU)
     return fa_plan_create_elem(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags, elem,
                                out);
-  const char* who = "fa_plan_create_order_elem";
-  int rc = fa_host::check_flags(who, flags);
-  if (rc) return rc;
+  return order_elem_plan("fa_plan_create_order_elem", seg32, nseg32, f32_numel, seg64, nseg64,
+                         i64_numel, n, order, flags, elem, elem, out);
+}
+
+int fa_plan_create_order_elem_out(const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                                  const fa_seg* seg64, int nseg64, int64_t i64_numel, int n,
+                                  int order, unsigned flags, int elem, int out_elem,
+                                  fa_plan** out) {
+  if (out_elem == elem)
+    return fa_plan_create_order_elem(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order,
+                                     flags, elem, out);
+  if (order == FA_ORDER_TORCH_CPU)
+    return fa_plan_create_elem_out(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags,
+                                   elem, out_elem, out);
+  const char* who = "fa_plan_create_order_elem_out";
   if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
   *out = nullptr;
-  // the planner's one device input: the S = 1 launch's resident workgroups
-  // (asked only for an element type that has a kernel; the checks below
-  // refuse every other)
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  const bool known = elem == FA_ELEM_F16 || elem == FA_ELEM_BF16;
-  const int slots =
-      e == hipSuccess && known && !(flags & FA_PLAN_TUNE_NO_BALANCE) ? tgpu16_slots(dev, elem) : 0;
-  fa_host::Layout l;
-  fa_host::TgpuTables t;
-  rc = fa_host::plan_order_elem(who, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order,
-                                flags, elem, slots, &l, &t);
-  if (rc) return rc;
-  PlanPtr p(new fa_plan());
-  for (int g = 0; g < 6; ++g) p->tg_lo[g] = t.lo[g];
-  p->info = l.info;
-  p->info.ntiles = (int32_t)t.tiles.size();
-  p->info.ntiles_tail = (int32_t)t.tiles.size();
-  p->flags = flags;
-  p->elem = p->out_elem = elem;
-  p->vec_u = 1;
-  p->flat_bcast = fa_host::flat_bcast_ok(flags, l, elem, elem);
-  p->order = FA_ORDER_TORCH_GPU;
-  p->order_n = n;
-  set_kinds(p.get(), t.tiles);
-  p->device = dev;
-  // (no LDS reservation on the S = 2 launch: tgpu_s2_lds was measured on the
-  // fp32 instance only)
-  if (e == hipSuccess) e = upload(&p->d_tiles, t.tiles);
-  if (e == hipSuccess) e = upload(&p->d_fac, t.fac);
-  if (e != hipSuccess) return set_err(FA_E_HIP, "%s: %s", who, hipGetErrorString(e));
-  *out = p.release();
-  return FA_OK;
+  if (!((elem == FA_ELEM_F16 || elem == FA_ELEM_BF16) && out_elem == FA_ELEM_F32))
+    return set_err(FA_E_INVAL, "%s: out_elem must equal elem, or be FA_ELEM_F32 over FA_ELEM_F16 / "
+                               "FA_ELEM_BF16 clients (got elem %d, out_elem %d)", who, elem,
+                   out_elem);
+  return order_elem_plan(who, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order, flags,
+                         elem, out_elem, out);
 }
 
 namespace {
@@ -1639,7 +1674,9 @@ hipError_t run_tgpu(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipSt
 
 // a 16-bit torch-GPU-order plan (fa_plan_create_order_elem): one launch of
 // fedagg_tgpu16.hip's kernels per row-split group, then the flat byte copy
-// of the result bucket (fa_reduce_tab has refused a plan without coverage)
+// of the result bucket (fa_reduce_tab has refused a plan without coverage);
+// with an fp32 result bucket (fa_plan_create_order_elem_out) their wide-store
+// instances, then the narrowing broadcast
 hipError_t run_tgpu16(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipStream_t st) {
   hipError_t e = hipSuccess;
   for (int g = 0; g < 5 && e == hipSuccess; ++g) {
@@ -1648,7 +1685,7 @@ hipError_t run_tgpu16(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hip
     a.tiles = plan->d_tiles + lo;
     a.tfac = plan->d_fac + lo;
     a.ntiles = cnt;
-    e = fa_tgpu16::launch(a, g, cnt, plan->elem, st);
+    e = fa_tgpu16::launch(a, g, cnt, plan->elem, plan->out_elem == FA_ELEM_F32, st);
   }
   if (e == hipSuccess && bcast && plan->tg_lo[5] > 0) {
     a.tiles = plan->d_tiles;

@@ -11,7 +11,11 @@
 // over the parts; the lane tree for M == 1), the sum is multiplied by
 // float(M) / float(N M), and the fp32 value is rounded to nearest-even into
 // the key's type.  The kernels read the clients' 16-bit buckets directly and
-// write a 16-bit result.
+// write a 16-bit result.  WIDE instances (fa_plan_create_order_elem_out, an
+// fp32 master global over 16-bit clients) differ in the finish alone: the
+// fp32 value sum times factor is stored unrounded into an fp32 bucket at the
+// same element offsets, and fedagg_h16.hip's narrowing broadcast then rounds
+// it into the clients' buckets.
 //
 // Its own translation unit and its own kernel family (DESIGN §4.1:
 // tgpu_kernel and reduce_impl.h are not templated on the element type).  The
@@ -49,6 +53,13 @@ __device__ __forceinline__ void st_sc1(uint16_t* base, uint32_t vidx, u4 v) {
       __builtin_amdgcn_make_buffer_rsrc(base, (short)0, 0x7fffffff, 0x00020000);
   __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)(16 * vidx), 0, 16);
 }
+// The wide result store (an fp32 result bucket): one 16-B store of fp32 at
+// byte offset `off` past a uniform base, the same policy.
+__device__ __forceinline__ void st_sc1_f4(float* base, uint32_t off, f4 v) {
+  const __amdgpu_buffer_rsrc_t r =
+      __builtin_amdgcn_make_buffer_rsrc(base, (short)0, 0x7fffffff, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, 16);
+}
 // Client i's 16-bit bucket through scalar loads only (reduce_impl.h sptr32).
 __device__ __forceinline__ const uint16_t* sptr16(KArgs& a, int i) {
   return (const uint16_t*)sptr32(a, i);
@@ -65,6 +76,10 @@ __device__ __forceinline__ float mean32(float s, float fac) {
 }
 __device__ __forceinline__ f4 mean32x4(f4 s, float fac) {
   return f4{mean32(s.x, fac), mean32(s.y, fac), mean32(s.z, fac), mean32(s.w, fac)};
+}
+// ... of a WIDE instance: stored as it is, so there is nothing to fold into
+__device__ __forceinline__ f4 wide32x4(f4 s, float fac) {
+  return f4{__fmul_rn(s.x, fac), __fmul_rn(s.y, fac), __fmul_rn(s.z, fac), __fmul_rn(s.w, fac)};
 }
 
 // The value the scalar orders read from a 16-bit bucket: widened exactly.
@@ -160,10 +175,51 @@ __device__ __forceinline__ F8 zero8() {
   return F8{z, z};
 }
 __device__ __forceinline__ F8 add8(F8 x, F8 y) { return F8{add4(x.lo, y.lo), add4(x.hi, y.hi)}; }
-// factor, round to nearest-even, one 16-B store
-template <int EL>
+// factor, round to nearest-even, one 16-B store (WIDE: the lane's 8 fp32
+// values as two 16-B stores at float offset start + 8 vi — the form
+// finish8_xchg below replaces on wide tiles)
+template <int EL, bool WIDE>
 __device__ __forceinline__ void finish8(KArgs& a, int64_t start, uint32_t vi, F8 r, float fac) {
-  st_sc1((uint16_t*)a.out32 + start, vi, narrow8<EL>(mean32x4(r.lo, fac), mean32x4(r.hi, fac)));
+  if constexpr (WIDE) {
+    st_sc1_f4(a.out32 + start, 32 * vi, wide32x4(r.lo, fac));
+    st_sc1_f4(a.out32 + start, 32 * vi + 16, wide32x4(r.hi, fac));
+  } else {
+    st_sc1((uint16_t*)a.out32 + start, vi, narrow8<EL>(mean32x4(r.lo, fac), mean32x4(r.hi, fac)));
+  }
+}
+
+// The WIDE finish after an exchange inside the wave (fedagg_h16.hip
+// tile_vec16's): a lane's 8 fp32 results are 32 B, and stored from the lane
+// that summed them each store instruction covers only every other 16 B of the
+// wave's 2 KB.  For store s, lane t takes half t & 1 of lane 32 s + t / 2, and
+// each store instruction writes 1 KB contiguous, as the 16-bit result store
+// does.  Every lane of the workgroup takes part (one past the tile's end holds
+// +0 sums); a store goes out when its SOURCE lane is inside.  Stored from
+// the summing lane the launch ran 13.2 us behind at N = 5 (39.5 against
+// 26.3 us), 9.5 us at N = 20, 6.6 us at N = 32 and 3 us at N = 64
+// (profiles/tgpu16_master_finish.jsonl).
+// (FA_TGPU16_WIDE_XCHG: 0 stores from the summing lane, for that A/B:
+// tools/tgpu16_ab.py kernel --master 1 --tree)
+#ifndef FA_TGPU16_WIDE_XCHG
+#define FA_TGPU16_WIDE_XCHG 1
+#endif
+__device__ __forceinline__ f4 shfl4(f4 v, int src) {
+  return f4{__shfl(v.x, src, 64), __shfl(v.y, src, 64), __shfl(v.z, src, 64),
+            __shfl(v.w, src, 64)};
+}
+template <bool FULL>
+__device__ __forceinline__ void finish8_xchg(KArgs& a, int64_t start, int count, F8 r, float fac) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wv0 = threadIdx.x - lane;  // the wave's first vector
+  const f4 lo = wide32x4(r.lo, fac), hi = wide32x4(r.hi, fac);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const uint32_t src = 32 * s + (lane >> 1);
+    const f4 l = shfl4(lo, (int)src), h = shfl4(hi, (int)src);
+    const f4 v = (lane & 1) ? h : l;
+    if (FULL || (int)(kVec * (wv0 + src)) < count)
+      st_sc1_f4(a.out32 + start, 32 * wv0 + 1024 * s + 16 * lane, v);
+  }
 }
 
 // S = 1 or 2 over tiles of up to 2048 elements, one 16-B load per lane per
@@ -191,7 +247,7 @@ __device__ __forceinline__ void finish8(KArgs& a, int64_t start, uint32_t vi, F8
 #ifndef FA_TGPU16_S2_PASSES
 #define FA_TGPU16_S2_PASSES 1
 #endif
-template <int EL, int S, bool FULL, bool PASSES>
+template <int EL, int S, bool FULL, bool PASSES, bool WIDE>
 __device__ __forceinline__ void wide16(KArgs& a, int64_t start, int count, float fac) {
   static_assert(S == 1 || S == 2, "row split of the wide loop");
   constexpr int R = 4 * S;
@@ -248,10 +304,16 @@ __device__ __forceinline__ void wide16(KArgs& a, int64_t start, int count, float
       }
     }
   }
+  if constexpr (WIDE && FA_TGPU16_WIDE_XCHG != 0) {
+    F8 r = add8(add8(add8(acc[0], acc[1]), acc[2]), acc[3]);
+    if constexpr (S == 2) r = add8(r, add8(add8(add8(acc[4], acc[5]), acc[6]), acc[7]));
+    finish8_xchg<FULL>(a, start, count, r, fac);
+    return;
+  }
   if (!FULL && !ok) return;
   F8 r = add8(add8(add8(acc[0], acc[1]), acc[2]), acc[3]);
   if constexpr (S == 2) r = add8(r, add8(add8(add8(acc[4], acc[5]), acc[6]), acc[7]));
-  finish8<EL>(a, start, vi, r, fac);
+  finish8<EL, WIDE>(a, start, vi, r, fac);
 }
 
 // ---------------------------------------------------------- S >= 4 tiles ---
@@ -308,10 +370,19 @@ __device__ __forceinline__ f4 outer4(KArgs& a, int64_t start, uint32_t v, int n)
   return val[0];
 }
 
-// A V tile (4 elements per lane per pass, 8-B sc1 result stores) and a
-// scalar tile (one element per lane) of row split S.
-template <int EL, int S>
+// A V tile (4 elements per lane per pass, 8-B sc1 result stores; WIDE: one
+// 16-B store of the 4 fp32 values) and a scalar tile (one element per lane;
+// WIDE: a 4-B store) of row split S.
+template <int EL, int S, bool WIDE>
 __device__ __forceinline__ void v_tile(KArgs& a, const Tile& t, float fac) {
+  if constexpr (WIDE) {
+    for (int h = 0; h < kTile / (4 * kBlock); ++h) {
+      const uint32_t v = threadIdx.x + h * kBlock;
+      if ((int)(v * 4) >= t.count) return;
+      st_sc1_f4(a.out32 + t.start, 16 * v, wide32x4(outer4<EL, S>(a, t.start, v, a.n), fac));
+    }
+    return;
+  }
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       (uint16_t*)a.out32 + t.start, (short)0, 0x7fffffff, 0x00020000);
   for (int h = 0; h < kTile / (4 * kBlock); ++h) {
@@ -322,14 +393,15 @@ __device__ __forceinline__ void v_tile(KArgs& a, const Tile& t, float fac) {
     __builtin_amdgcn_raw_buffer_store_b64(w, rs, (int)(8 * v), 0, 16);
   }
 }
-template <int EL, int S>
+template <int EL, int S, bool WIDE>
 __device__ __forceinline__ void scalar_tile(KArgs& a, const Tile& t, float fac) {
   const int j = threadIdx.x;
   if (j >= t.count) return;
   const int64_t e = t.start + j;
   if ((t.kind & 0xFF) == K_F32_TGPU) {
     const float s = tgpu_outer<Src16<EL>, S>(Src16<EL>{a}, e, a.n);
-    ((uint16_t*)a.out32)[e] = (uint16_t)narrow<EL>(mean32(s, fac));
+    if constexpr (WIDE) a.out32[e] = __fmul_rn(s, fac);
+    else ((uint16_t*)a.out32)[e] = (uint16_t)narrow<EL>(mean32(s, fac));
   } else {
     a.out64[e] = (int64_t)__fmul_rn(tgpu_outer<SrcI64, S>(SrcI64{a}, e, a.n), fac);
   }
@@ -339,8 +411,8 @@ __device__ __forceinline__ void scalar_tile(KArgs& a, const Tile& t, float fac) 
 // fedagg.hip's tgpu_kernel<LS>: the plan groups its tiles by S and launches
 // each group; inner tiles (M == 1) ride in the LS = 0 group; when the S = 2
 // group is the largest, the S = 1 and S = 4 tiles and the inner tiles ride
-// in its launch.
-template <int EL, int LS>
+// in its launch.  WIDE: the fp32-store form of the same kernel.
+template <int EL, int LS, bool WIDE>
 __global__ __launch_bounds__(kBlock) void tgpu16_kernel(ReduceArgs args) {
   (void)args;
   constexpr int S = 1 << LS;
@@ -353,8 +425,8 @@ __global__ __launch_bounds__(kBlock) void tgpu16_kernel(ReduceArgs args) {
   if constexpr (LS == 0) {
     if (base == K_F32_TGPU_W) {
       constexpr bool P = FA_TGPU16_S1_PASSES != 0;
-      if (t.count == kTile) wide16<EL, 1, true, P>(a, t.start, t.count, fac);
-      else wide16<EL, 1, false, P>(a, t.start, t.count, fac);
+      if (t.count == kTile) wide16<EL, 1, true, P, WIDE>(a, t.start, t.count, fac);
+      else wide16<EL, 1, false, P, WIDE>(a, t.start, t.count, fac);
       return;
     }
   }
@@ -362,27 +434,27 @@ __global__ __launch_bounds__(kBlock) void tgpu16_kernel(ReduceArgs args) {
     if (base == K_F32_TGPU_W) {
       constexpr bool P = FA_TGPU16_S2_PASSES != 0;
       if (ls == 0) {
-        if (t.count == kTile) wide16<EL, 1, true, P>(a, t.start, t.count, fac);
-        else wide16<EL, 1, false, P>(a, t.start, t.count, fac);
+        if (t.count == kTile) wide16<EL, 1, true, P, WIDE>(a, t.start, t.count, fac);
+        else wide16<EL, 1, false, P, WIDE>(a, t.start, t.count, fac);
       } else {
-        if (t.count == kTile) wide16<EL, 2, true, P>(a, t.start, t.count, fac);
-        else wide16<EL, 2, false, P>(a, t.start, t.count, fac);
+        if (t.count == kTile) wide16<EL, 2, true, P, WIDE>(a, t.start, t.count, fac);
+        else wide16<EL, 2, false, P, WIDE>(a, t.start, t.count, fac);
       }
       return;
     }
     if (!inner && ls != 1) {  // a rider: S = 1 or 4
-      if (base == K_F32_TGPU_V) v_tile<EL, 4>(a, t, fac);
-      else if (ls == 0) scalar_tile<EL, 1>(a, t, fac);
-      else scalar_tile<EL, 4>(a, t, fac);
+      if (base == K_F32_TGPU_V) v_tile<EL, 4, WIDE>(a, t, fac);
+      else if (ls == 0) scalar_tile<EL, 1, WIDE>(a, t, fac);
+      else scalar_tile<EL, 4, WIDE>(a, t, fac);
       return;
     }
   }
   if (base == K_F32_TGPU_V) {
-    if constexpr (S >= 4) v_tile<EL, S>(a, t, fac);  // (S <= 2 keys make W tiles)
+    if constexpr (S >= 4) v_tile<EL, S, WIDE>(a, t, fac);  // (S <= 2 keys make W tiles)
     return;
   }
   if (base == K_F32_TGPU || base == K_I64_TGPU) {
-    scalar_tile<EL, S>(a, t, fac);
+    scalar_tile<EL, S, WIDE>(a, t, fac);
     return;
   }
   if (!inner) return;
@@ -395,7 +467,11 @@ __global__ __launch_bounds__(kBlock) void tgpu16_kernel(ReduceArgs args) {
   if (base == K_F32_TGPU_IN) {
     const float s = vec ? tgpu_inner_vec(Src16<EL>{a}, e, n, bw, lane)
                         : tgpu_inner(Src16<EL>{a}, e, n, bw, lane);
-    if (lane == 0) ((uint16_t*)a.out32)[e] = (uint16_t)narrow<EL>(mean32(s, fac));
+    if constexpr (WIDE) {
+      if (lane == 0) a.out32[e] = __fmul_rn(s, fac);
+    } else {
+      if (lane == 0) ((uint16_t*)a.out32)[e] = (uint16_t)narrow<EL>(mean32(s, fac));
+    }
   } else {
     const float s = vec ? tgpu_inner_vec(SrcI64{a}, e, n, bw, lane)
                         : tgpu_inner(SrcI64{a}, e, n, bw, lane);
@@ -403,38 +479,48 @@ __global__ __launch_bounds__(kBlock) void tgpu16_kernel(ReduceArgs args) {
   }
 }
 
-template <int EL>
+template <int EL, bool WIDE>
 static hipError_t launch_el(const ReduceArgs& a, int group, int ntiles, hipStream_t st) {
   const dim3 g(ntiles), b(kBlock);
   // no LDS reservation on the S = 2 launch: fedagg.hip's tgpu_s2_lds was
   // measured on the fp32 instance only
   switch (group) {
-    case 0: hipLaunchKernelGGL((tgpu16_kernel<EL, 0>), g, b, 0, st, a); break;
-    case 1: hipLaunchKernelGGL((tgpu16_kernel<EL, 1>), g, b, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((tgpu16_kernel<EL, 2>), g, b, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((tgpu16_kernel<EL, 3>), g, b, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((tgpu16_kernel<EL, 4>), g, b, 0, st, a); break;
+    case 0: hipLaunchKernelGGL((tgpu16_kernel<EL, 0, WIDE>), g, b, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((tgpu16_kernel<EL, 1, WIDE>), g, b, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((tgpu16_kernel<EL, 2, WIDE>), g, b, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((tgpu16_kernel<EL, 3, WIDE>), g, b, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((tgpu16_kernel<EL, 4, WIDE>), g, b, 0, st, a); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
-hipError_t launch(const ReduceArgs& a, int group, int ntiles, int elem, hipStream_t st) {
+hipError_t launch(const ReduceArgs& a, int group, int ntiles, int elem, bool wide,
+                  hipStream_t st) {
   if (ntiles <= 0) return hipSuccess;
-  if (elem == FA_ELEM_F16) return launch_el<FA_ELEM_F16>(a, group, ntiles, st);
-  if (elem == FA_ELEM_BF16) return launch_el<FA_ELEM_BF16>(a, group, ntiles, st);
+  if (elem == FA_ELEM_F16)
+    return wide ? launch_el<FA_ELEM_F16, true>(a, group, ntiles, st)
+                : launch_el<FA_ELEM_F16, false>(a, group, ntiles, st);
+  if (elem == FA_ELEM_BF16)
+    return wide ? launch_el<FA_ELEM_BF16, true>(a, group, ntiles, st)
+                : launch_el<FA_ELEM_BF16, false>(a, group, ntiles, st);
   return hipErrorInvalidValue;
 }
 
-int occupancy_s1(int elem) {
+template <bool WIDE>
+static int occupancy_s1_w(int elem) {
   int occ = 0;
   const hipError_t e =
       elem == FA_ELEM_F16
-          ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tgpu16_kernel<FA_ELEM_F16, 0>,
+          ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tgpu16_kernel<FA_ELEM_F16, 0, WIDE>,
                                                          kBlock, 0)
-          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tgpu16_kernel<FA_ELEM_BF16, 0>,
+          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tgpu16_kernel<FA_ELEM_BF16, 0, WIDE>,
                                                          kBlock, 0);
   return e == hipSuccess ? occ : 0;
+}
+
+int occupancy_s1(int elem, bool wide) {
+  return wide ? occupancy_s1_w<true>(elem) : occupancy_s1_w<false>(elem);
 }
 
 }  // namespace fa_tgpu16

@@ -314,7 +314,7 @@ int fa_plan_create_order(const fa_seg *seg32, int nseg32, int64_t f32_numel,
  *   to nearest-even into the 16-bit type (a NaN is a NaN).  Offsets, counts
  *   and f32_numel are in 16-bit ELEMENTS; vector tiles start and end on 16-B
  *   boundaries (8 elements) and hold up to 2048 elements.  Result type ==
- *   elem (no mixed form).  The argument checks and messages are the two
+ *   elem (an fp32 result: fa_plan_create_order_elem_out).  The argument checks and messages are the two
  *   parents' (FA_E_RANGE for n outside 2..FA_MAX_CLIENTS and for a key
  *   "outside the restated configurations").  fa_reduce / fa_reduce_tab on
  *   such a plan refuse with FA_E_INVAL, before any launch or allocation and
@@ -325,6 +325,36 @@ int fa_plan_create_order_elem(const fa_seg *seg32, int nseg32,
                               int64_t f32_numel, const fa_seg *seg64,
                               int nseg64, int64_t i64_numel, int n, int order,
                               unsigned flags, int elem, fa_plan **out);
+/* ... with the result in a bucket of `out_elem` elements (FA_ELEM_*): the
+ * round of an fp32 master global over 16-bit clients in either order.
+ * out_elem == elem: fa_plan_create_order_elem exactly.
+ * order FA_ORDER_TORCH_CPU: fa_plan_create_elem_out exactly (tile_elems 0).
+ * elem FA_ELEM_F16 / FA_ELEM_BF16 with out_elem FA_ELEM_F32 and
+ *   FA_ORDER_TORCH_GPU: the reference's stack([c[k].float() ...], 0).mean(0)
+ *   on device tensors of 16-bit clients, stored unrounded into the global's
+ *   fp32 key, then load_state_dict's copy_ rounding it to nearest-even into
+ *   each client's 16-bit key.  The table is the one
+ *   fa_plan_build_order_host_elem returns for `elem` (S, the order and the
+ *   factor per key are the fp32 plan's); offsets, counts and f32_numel are in
+ *   ELEMENTS.  fa_reduce / fa_reduce_tab: c32[i] are the clients' 16-bit
+ *   buckets; out32 is an fp32 bucket of f32_numel floats (16-B aligned) that
+ *   takes the fp32 mean at the same element offsets.  FA_F_BCAST_ONLY rounds
+ *   out32 over [0, f32_numel) into every client's 16-bit bucket (padding
+ *   included) and copies the int64 bucket; FA_F_BCAST is the reduce, then
+ *   that broadcast; both need FA_PLAN_GAPS_ARE_PADDING and segments that
+ *   cover the bucket (no gap of >= 128 elements; any f32_numel).  Refused
+ *   with FA_E_INVAL, before any launch or allocation and with nothing
+ *   written: weights, n != the plan's n, FA_F_SUM_ONLY, a broadcast flag
+ *   without coverage; fa_reduce_chain refuses it as every 16-bit plan.
+ *   fa_plan_elem answers the clients' type, fa_plan_out_elem FA_ELEM_F32.
+ * Every other pair (an fp32 elem with a 16-bit out_elem, fp16 <-> bf16) is
+ * FA_E_INVAL.  The pair and the flags are checked before any device call;
+ * *out is cleared first. */
+int fa_plan_create_order_elem_out(const fa_seg *seg32, int nseg32,
+                                  int64_t f32_numel, const fa_seg *seg64,
+                                  int nseg64, int64_t i64_numel, int n,
+                                  int order, unsigned flags, int elem,
+                                  int out_elem, fa_plan **out);
 /* Host-only table of that plan (no device, no allocation; FA_ELEM_F32: the
  * fp32 torch-GPU-order table), for tests and inspection: the tiles in launch
  * order (kind: the tile kind, log2 S in bits 8-15, bit 16 the input-vectorised

@@ -18,8 +18,19 @@ one process, same buffers: wrn16_8 C10's shapes cast to bf16
         call only, so the same script measures another checkout of the
         package (--tree; --native16 0 there: the staged round).
 
+    --master 1 on either leg: an fp32 master global over the 16-bit clients
+        (DESIGN §4.13).  kernel: the 16-bit torch-GPU-order reduce, the
+        CPU-order mixed reduce (fa_plan_create_elem_out) and the
+        torch-GPU-order mixed reduce (fa_plan_create_order_elem_out) of the
+        same client buckets, the mixed ones into an fp32 bucket (4 B per
+        element written where the 16-bit one writes 2), and the ratio to the
+        16-bit torch-GPU-order time.  dropin: the global stays fp32;
+        --native16 2 sets native16_master=True too (--native16 1 on a
+        checkout from before that option: the staged round).
+
 Each record is one JSON line, appended to --out (default
-profiles/tgpu16_<leg>.jsonl) and printed.
+profiles/tgpu16_<leg>.jsonl, with --master profiles/tgpu16_master_<leg>.jsonl)
+and printed.
 """
 import argparse
 import ctypes
@@ -80,31 +91,45 @@ def kernel_leg(args):
         return f32, h16, i64
 
     for n in args.n:
-        plans = {
-            "f32_tgpu": _lib.Plan(lay32.segs32, lay32.f32_numel, lay32.segs64, lay32.i64_numel,
-                                  order=_lib.FA_ORDER_TORCH_GPU, n=n),
-            "h16_cpu": _lib.Plan(lay16.segs32, lay16.f32_numel, lay16.segs64, lay16.i64_numel,
-                                 elem=elem),
-            "h16_tgpu": _lib.Plan.for_order(lay16.segs32, lay16.f32_numel, lay16.segs64,
-                                            lay16.i64_numel, n=n, elem=elem),
-        }
+        if args.master:
+            plans = {
+                "h16_tgpu": _lib.Plan.for_order(lay16.segs32, lay16.f32_numel, lay16.segs64,
+                                                lay16.i64_numel, n=n, elem=elem),
+                "mix_cpu": _lib.Plan(lay16.segs32, lay16.f32_numel, lay16.segs64,
+                                     lay16.i64_numel, elem=elem, out_elem=_lib.FA_ELEM_F32),
+                "mix_tgpu": _lib.Plan.for_order(lay16.segs32, lay16.f32_numel, lay16.segs64,
+                                                lay16.i64_numel, n=n, elem=elem,
+                                                out_elem=_lib.FA_ELEM_F32),
+            }
+        else:
+            plans = {
+                "f32_tgpu": _lib.Plan(lay32.segs32, lay32.f32_numel, lay32.segs64,
+                                      lay32.i64_numel, order=_lib.FA_ORDER_TORCH_GPU, n=n),
+                "h16_cpu": _lib.Plan(lay16.segs32, lay16.f32_numel, lay16.segs64,
+                                     lay16.i64_numel, elem=elem),
+                "h16_tgpu": _lib.Plan.for_order(lay16.segs32, lay16.f32_numel, lay16.segs64,
+                                                lay16.i64_numel, n=n, elem=elem),
+            }
         rot = max(1, -(-(1 << 30) // (n * 2 * lay16.f32_numel)))
         sets = []
         for _ in range(rot):
             slab.release()
-            with slab.expecting(2 * n + 2):
+            with slab.expecting(2 * n + 3):
                 cl = [client(c) for c in range(n)]
                 o32 = slab.carve(lay32.f32_numel, torch.float32, dev)
                 o16 = slab.carve(lay16.f32_numel, tdt, dev)
+                # the master global's bucket: fp32 at the 16-bit layout's offsets
+                om = slab.carve(lay16.f32_numel, torch.float32, dev)
             o64 = torch.zeros_like(cl[0][2])
             sets.append({
                 "f32": (_lib.ptr_array([c[0].data_ptr() for c in cl]), o32),
                 "h16": (_lib.ptr_array([c[1].data_ptr() for c in cl]), o16),
+                "mix": (_lib.ptr_array([c[1].data_ptr() for c in cl]), om),
                 "i64": (_lib.ptr_array([c[2].data_ptr() for c in cl]), o64), "keep": cl})
 
         def call(name, i):
             s = sets[i % rot]
-            p, o = s["f32" if name.startswith("f32") else "h16"]
+            p, o = s[name[:3]]
             p64, o64 = s["i64"]
             _lib.check(L.fa_reduce(plans[name].handle, p, p64, n, None, o.data_ptr(),
                                    o64.data_ptr(), 0, st), "fa_reduce")
@@ -124,14 +149,19 @@ def kernel_leg(args):
         rec = {"exp": "tgpu16_ab_kernel", "tree": args.label, "layout": args.layout, "dtype": args.dtype, "n": n,
                "rot": rot, "reps": reps, "rounds": args.rounds, "elems": lay16.f32_data_elems,
                "tiles": {k: p.info["ntiles"] for k, p in plans.items()}}
-        f32_med = median(times["f32_tgpu"])
+        base = "h16_tgpu" if args.master else "f32_tgpu"
+        base_med = median(times[base])
         for name in plans:
             nb = (lay32 if name.startswith("f32") else lay16).algorithmic_bytes(n)
+            if name.startswith("mix"):   # the result is written in fp32
+                nb += 2 * lay16.f32_data_elems
             med = median(times[name])
             rec[name] = {"us_median": round(med, 2), "us_min": round(min(times[name]), 2),
                          "us_max": round(max(times[name]), 2), "alg_bytes": nb,
-                         "gbps": round(nb / med / 1e3, 1), "vs_f32": round(med / f32_med, 4)}
-        emit(rec, args.out or os.path.join(ROOT, "profiles", "tgpu16_kernel.jsonl"))
+                         "gbps": round(nb / med / 1e3, 1),
+                         "vs_h16_tgpu" if args.master else "vs_f32": round(med / base_med, 4)}
+        emit(rec, args.out or os.path.join(
+            ROOT, "profiles", "tgpu16_master_kernel.jsonl" if args.master else "tgpu16_kernel.jsonl"))
         del sets, plans
         torch.cuda.empty_cache()
 
@@ -161,7 +191,7 @@ def dropin_leg(args):
     torch.cuda.set_device(dev)
     gen = torch.Generator().manual_seed(1)
 
-    def model(c):
+    def model(c, fp32=False):
         m = ManifestModule(man)
         with torch.no_grad():
             for v in m.state_dict().values():
@@ -169,10 +199,12 @@ def dropin_leg(args):
                     v.copy_(torch.randn(v.shape, generator=gen) * 0.05)
                 else:
                     v.fill_(100 + c)
-        return m.to(tdt).to(dev)
-    g = model(0)
+        return (m if fp32 else m.to(tdt)).to(dev)
+    g = model(0, fp32=bool(args.master))
     clients = [model(c + 1) for c in range(n)]
-    if args.native16:
+    if args.native16 == 2:
+        feddct_amd.set_summation_order("torch_gpu", native16=True, native16_master=True)
+    elif args.native16:
         feddct_amd.set_summation_order("torch_gpu", native16=True)
     else:   # (a checkout from before the option: the staged round)
         feddct_amd.set_summation_order("torch_gpu")
@@ -190,13 +222,15 @@ def dropin_leg(args):
     for v in g.state_dict().values():
         sha.update(v.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes())
     rec = {"exp": "tgpu16_ab_dropin", "tree": args.label, "native16": bool(args.native16),
+           "native16_master": args.native16 == 2, "master": bool(args.master),
            "layout": args.layout, "dtype": args.dtype, "n": n, "calls": args.calls,
            "bucket_dtype": str(a.f32.dtype) if a is not None else None,
            "staged_keys": len(a._packed) if a is not None else None,
            "global_sha256": sha.hexdigest()[:16],
            "wall_us_median": round(median(ts), 1), "wall_us_min": round(min(ts), 1),
            "wall_us_max": round(max(ts), 1)}
-    emit(rec, args.out or os.path.join(ROOT, "profiles", "tgpu16_dropin.jsonl"))
+    emit(rec, args.out or os.path.join(
+        ROOT, "profiles", "tgpu16_master_dropin.jsonl" if args.master else "tgpu16_dropin.jsonl"))
 
 
 def main():
@@ -207,7 +241,9 @@ def main():
     ap.add_argument("--layout", default="wrn16_8_c10")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--calls", type=int, default=50)
-    ap.add_argument("--native16", type=int, default=1)
+    ap.add_argument("--native16", type=int, default=1,
+                    help="0: option off; 1: native16=True; 2: native16_master=True too")
+    ap.add_argument("--master", type=int, default=0, help="1: an fp32 master global")
     ap.add_argument("--tree", default=ROOT, help="checkout whose feddct_amd package is measured")
     ap.add_argument("--label", default="this tree", help="name of --tree in the record")
     ap.add_argument("--out", default=None)
