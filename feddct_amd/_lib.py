@@ -280,54 +280,60 @@ class Plan:
     def __init__(self, segs32, f32_numel, segs64=(), i64_numel=0, tile_elems=0,
                  flags=FA_PLAN_GAPS_ARE_PADDING, tiles=None, order=FA_ORDER_TORCH_CPU, n=0,
                  elem=FA_ELEM_F32, out_elem=None):
-        h = ctypes.c_void_p()
-        self.elem = int(elem)
-        # the result bucket's element type (fa_plan_create_elem_out): FA_ELEM_F32
-        # over 16-bit clients is the mixed plan of an fp32 master global
-        self.out_elem = self.elem if out_elem is None else int(out_elem)
-        if out_elem is not None:
-            if order != FA_ORDER_TORCH_CPU or tiles is not None:
-                raise FedaggError("a plan with an output element type is cut from a layout's "
-                                  "segments in torch's CPU order (no tile subsets, no torch-GPU "
-                                  "order)")
-            a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
-            a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
-            check(lib.fa_plan_create_elem_out(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
-                                              int(tile_elems), flags, int(elem), int(out_elem),
-                                              ctypes.byref(h)), "fa_plan_create_elem_out")
-        elif elem != FA_ELEM_F32:
+        # out_elem: the result bucket's element type (fa_plan_create_elem_out);
+        # FA_ELEM_F32 over 16-bit clients is the mixed plan of an fp32 master global
+        if out_elem is not None and (order != FA_ORDER_TORCH_CPU or tiles is not None):
+            raise FedaggError("a plan with an output element type is cut from a layout's "
+                              "segments in torch's CPU order (no tile subsets, no torch-GPU "
+                              "order)")
+        if elem != FA_ELEM_F32 and (order != FA_ORDER_TORCH_CPU or tiles is not None):
             # a 16-bit floating bucket: the CPU order from a segment list only
-            if order != FA_ORDER_TORCH_CPU or tiles is not None:
-                raise FedaggError("a 16-bit plan is cut from a layout's segments in torch's "
-                                  "CPU order (no tile subsets, no torch-GPU order)")
-            a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
-            a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
-            check(lib.fa_plan_create_elem(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
-                                          int(tile_elems), flags, int(elem), ctypes.byref(h)),
-                  "fa_plan_create_elem")
-        elif order != FA_ORDER_TORCH_CPU:
-            a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
-            a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
-            check(lib.fa_plan_create_order(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
-                                           int(n), int(order), flags, ctypes.byref(h)),
-                  "fa_plan_create_order")
-        elif tiles is not None:
+            raise FedaggError("a 16-bit plan is cut from a layout's segments in torch's "
+                              "CPU order (no tile subsets, no torch-GPU order)")
+        self._create(segs32, f32_numel, segs64, i64_numel, tile_elems, flags, tiles, order, n,
+                     elem, out_elem)
+
+    def _create(self, segs32, f32_numel, segs64, i64_numel, tile_elems, flags, tiles, order, n,
+                elem, out_elem):
+        """The one path to a handle: a tile subset through
+        fa_plan_create_from_tiles_elem, a CPU-order segment plan through
+        fa_plan_create_elem_out (the entry that takes ``tile_elems``), any
+        other order through fa_plan_create_order_elem_out; the library forwards
+        each to the entry the arguments name.  That entry, which names itself
+        in the library's message, is the FedaggError's prefix."""
+        self.elem = int(elem)
+        self.out_elem = self.elem if out_elem is None else int(out_elem)
+        sizes, types = (int(f32_numel), int(i64_numel)), (self.elem, self.out_elem)
+        suffix = "" if types == (FA_ELEM_F32, FA_ELEM_F32) else "_elem"
+        h = ctypes.c_void_p()
+        if tiles is not None and order == FA_ORDER_TORCH_CPU:   # (an order is cut from segments)
             tiles = np.asarray(tiles, np.int64).reshape(-1, 3)
             arr = (FaTileDesc * max(1, len(tiles)))()
             for i, (s, c, k) in enumerate(tiles):
                 arr[i].start, arr[i].count, arr[i].kind = int(s), int(c), int(k)
-            check(lib.fa_plan_create_from_tiles(arr, len(tiles), int(f32_numel), int(i64_numel),
-                                                int(tile_elems), flags, ctypes.byref(h)),
-                  "fa_plan_create_from_tiles")
+            rc = lib.fa_plan_create_from_tiles_elem(arr, len(tiles), *sizes, int(tile_elems),
+                                                    flags, *types, ctypes.byref(h))
+            name = "fa_plan_create_from_tiles" + suffix
         else:
+            if self.out_elem != self.elem:
+                suffix = "_elem_out"
             a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
             a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
-            check(lib.fa_plan_create(a32, n32, int(f32_numel), a64, n64, int(i64_numel),
-                                     int(tile_elems), flags, ctypes.byref(h)), "fa_plan_create")
+            layout = (a32, n32, sizes[0], a64, n64, sizes[1])
+            if order == FA_ORDER_TORCH_CPU:
+                rc = lib.fa_plan_create_elem_out(*layout, int(tile_elems), flags, *types,
+                                                 ctypes.byref(h))
+                name = "fa_plan_create" + suffix
+            else:
+                rc = lib.fa_plan_create_order_elem_out(*layout, int(n), int(order), flags, *types,
+                                                       ctypes.byref(h))
+                name = "fa_plan_create_order" + suffix
+        check(rc, name)
         self.handle = h
         info = FaPlanInfo()
         check(lib.fa_plan_get_info(h, ctypes.byref(info)), "fa_plan_get_info")
         self.info = {f: getattr(info, f) for f, _ in FaPlanInfo._fields_}
+        return self
 
     @classmethod
     def from_tiles(cls, tiles, f32_numel, i64_numel=0, tile_elems=0,
@@ -336,23 +342,8 @@ class Plan:
         layout's table, of any element type (fa_plan_create_from_tiles_elem):
         fp32, 16-bit (``elem`` FA_ELEM_F16 / FA_ELEM_BF16), or mixed
         (``out_elem`` FA_ELEM_F32 over 16-bit clients)."""
-        self = cls.__new__(cls)
-        self.elem = int(elem)
-        self.out_elem = self.elem if out_elem is None else int(out_elem)
-        tiles = np.asarray(tiles, np.int64).reshape(-1, 3)
-        arr = (FaTileDesc * max(1, len(tiles)))()
-        for i, (s, c, k) in enumerate(tiles):
-            arr[i].start, arr[i].count, arr[i].kind = int(s), int(c), int(k)
-        h = ctypes.c_void_p()
-        check(lib.fa_plan_create_from_tiles_elem(arr, len(tiles), int(f32_numel), int(i64_numel),
-                                                 int(tile_elems), flags, self.elem, self.out_elem,
-                                                 ctypes.byref(h)),
-              "fa_plan_create_from_tiles_elem")
-        self.handle = h
-        info = FaPlanInfo()
-        check(lib.fa_plan_get_info(h, ctypes.byref(info)), "fa_plan_get_info")
-        self.info = {f: getattr(info, f) for f, _ in FaPlanInfo._fields_}
-        return self
+        return cls.__new__(cls)._create((), f32_numel, (), i64_numel, tile_elems, flags, tiles,
+                                        FA_ORDER_TORCH_CPU, 0, elem, out_elem)
 
     @classmethod
     def for_order(cls, segs32, f32_numel, segs64=(), i64_numel=0, n=0,
@@ -364,27 +355,8 @@ class Plan:
         ``out_elem``: the result bucket's element type
         (fa_plan_create_order_elem_out): FA_ELEM_F32 over 16-bit clients is
         the plan of an fp32 master global in that order."""
-        self = cls.__new__(cls)
-        self.elem = int(elem)
-        self.out_elem = self.elem if out_elem is None else int(out_elem)
-        a32, n32 = seg_array(segs32 if len(segs32) else np.zeros((0, 2), np.int64))
-        a64, n64 = seg_array(segs64 if len(segs64) else np.zeros((0, 2), np.int64))
-        h = ctypes.c_void_p()
-        if out_elem is None:
-            check(lib.fa_plan_create_order_elem(a32, n32, int(f32_numel), a64, n64,
-                                                int(i64_numel), int(n), int(order), flags,
-                                                int(elem), ctypes.byref(h)),
-                  "fa_plan_create_order_elem")
-        else:
-            check(lib.fa_plan_create_order_elem_out(a32, n32, int(f32_numel), a64, n64,
-                                                    int(i64_numel), int(n), int(order), flags,
-                                                    int(elem), int(out_elem), ctypes.byref(h)),
-                  "fa_plan_create_order_elem_out")
-        self.handle = h
-        info = FaPlanInfo()
-        check(lib.fa_plan_get_info(h, ctypes.byref(info)), "fa_plan_get_info")
-        self.info = {f: getattr(info, f) for f, _ in FaPlanInfo._fields_}
-        return self
+        return cls.__new__(cls)._create(segs32, f32_numel, segs64, i64_numel, 0, flags, None,
+                                        order, n, elem, out_elem)
 
     def launch_shape(self, n, weighted=False):
         """(tiles, resident-workgroup slots) a plain fa_reduce call with n

@@ -253,41 +253,32 @@ class Engine:
         client layout under an fp32 master global (fp32 result bucket,
         fa_plan_create_elem_out; under the torch-GPU order
         fa_plan_create_order_elem_out)."""
-        if order == "torch_gpu":
-            key = (layout.signature, device.index, n) + (("<master>",) if master else ())
-            if key in self._gpu_plans:
-                self._gpu_plans.move_to_end(key)
-                return self._gpu_plans[key]
-            try:
-                with torch.cuda.device(device):
-                    if layout.native16:   # (bound only with native16_gpu_order)
-                        p = _lib.Plan.for_order(layout.segs32, layout.f32_numel, layout.segs64,
-                                                layout.i64_numel, n=n,
-                                                elem=_lib.ELEM_OF_DTYPE[layout.float_dtype],
-                                                out_elem=_lib.FA_ELEM_F32 if master else None)
-                    else:
-                        p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
-                                      layout.i64_numel, order=_lib.FA_ORDER_TORCH_GPU, n=n)
-            except _lib.FedaggError as e:
-                if "outside the restated" not in str(e):
-                    raise
-                p = None
-            self._gpu_plans[key] = p
-            while len(self._gpu_plans) > self.GPU_PLAN_CACHE:
-                self._gpu_plans.popitem(last=False)
-            return p
-        key = (layout.signature, device.index) + (("<master>",) if master else ())
-        p = self._plans.get(key)
-        if p is None:
+        gpu = order == "torch_gpu"
+        # CPU-order plans serve every n: an unbounded map per layout; the
+        # torch-GPU order's are cut per client count: the LRU
+        cache = self._gpu_plans if gpu else self._plans
+        key = (layout.signature, device.index) + ((n,) if gpu else ()) + \
+            (("<master>",) if master else ())
+        if key in cache:
+            if gpu:
+                cache.move_to_end(key)
+            return cache[key]
+        try:
             with torch.cuda.device(device):
-                if master:
-                    p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
-                                  layout.i64_numel, elem=_lib.ELEM_OF_DTYPE[layout.float_dtype],
-                                  out_elem=_lib.FA_ELEM_F32)
-                else:
-                    p = _lib.Plan(layout.segs32, layout.f32_numel, layout.segs64,
-                                  layout.i64_numel, elem=_lib.ELEM_OF_DTYPE[layout.float_dtype])
-            self._plans[key] = p
+                # (a native16 layout under the torch-GPU order: bound only
+                # with native16_gpu_order)
+                p = _lib.Plan.for_order(
+                    layout.segs32, layout.f32_numel, layout.segs64, layout.i64_numel, n=n,
+                    order=_lib.FA_ORDER_TORCH_GPU if gpu else _lib.FA_ORDER_TORCH_CPU,
+                    elem=_lib.ELEM_OF_DTYPE[layout.float_dtype],
+                    out_elem=_lib.FA_ELEM_F32 if master else None)
+        except _lib.FedaggError as e:
+            if not gpu or "outside the restated" not in str(e):
+                raise
+            p = None
+        cache[key] = p
+        while gpu and len(cache) > self.GPU_PLAN_CACHE:
+            cache.popitem(last=False)
         return p
 
     def layout_of(self, module: torch.nn.Module) -> BucketLayout:

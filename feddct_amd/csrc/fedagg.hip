@@ -818,6 +818,12 @@ int grid_for(int64_t work, int per_block) {
 
 }  // namespace
 
+// The kernel family a plan's calls launch, recorded once at creation: the
+// default fp32 reduce, the 16-bit reduce (fedagg_h16.hip; a mixed plan's
+// wide-store instances too), and the torch-GPU order over fp32 (tgpu_kernel)
+// and over 16-bit buckets (fedagg_tgpu16.hip).
+enum class FaFamily : int { kDefault = 0, kH16 = 1, kTgpu = 2, kTgpu16 = 3 };
+
 // The plan's host summary — device, flags, vec_u, and the device tables' own
 // counts nt / ns / nt_alt / ns_alt / bal[] (their scalar tiles are packed,
 // r03, K_SCALAR_PACKED; info.* keep the host view of the layout's tiles) —
@@ -846,8 +852,9 @@ struct fa_plan : fa_host::PlanShape {
   // on a mixed plan: 16-bit clients, FA_ELEM_F32 result (the fp32 master
   // global), the wide-store reduce and the narrowing broadcast
   int out_elem = FA_ELEM_F32;
-  int order = FA_ORDER_TORCH_CPU;
-  int order_n = 0;        // FA_ORDER_TORCH_GPU: the client count it was cut for
+  FaFamily family = FaFamily::kDefault;
+  bool tgpu() const { return family == FaFamily::kTgpu || family == FaFamily::kTgpu16; }
+  int order_n = 0;        // the torch-GPU order: the client count it was cut for
   int tgpu_batch = 16;    // ... rows per load batch of its S = 1 tiles (8 for N < 16)
   size_t tgpu_s2_lds = 0;  // ... the S = 2 launch's LDS reservation (tgpu_s2_lds)
   float* d_fac = nullptr; // ... and its per-tile mean factors
@@ -864,30 +871,88 @@ void set_kinds(fa_plan* p, const std::vector<Tile>& t) {
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-// Resident workgroups of the reduce kernel (U, B, deep, weighted) on device
-// `dev`, queried once per process (0: unknown -> the plain table).
-int kernel_slots(int dev, int u, int b, bool deep, bool w) {
+// Per-device memo of what the planners ask of a device, computed once per
+// process under one lock: `key` names the question (a user's tag plus its
+// own index), `value()` answers it.
+enum : int { kMemoReduce = 0, kMemoTgpu = 1 << 12, kMemoTgpu16 = 2 << 12, kMemoS2Lds = 3 << 12 };
+template <class F>
+int64_t dev_memo(int dev, int key, F value) {
   static std::mutex mu;
-  static std::map<int64_t, int> cache;
-  const int64_t key = ((((int64_t)dev * 8 + u) * 32 + b) * 2 + deep) * 2 + w;
+  static std::map<std::pair<int, int>, int64_t> cache;
   std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(key);
+  auto it = cache.find({dev, key});
   if (it != cache.end()) return it->second;
-  int occ = 0;
-  switch (u * 100 + b) {
-    case 108: occ = occupancy_u<1, 8>(deep, w); break;
-    case 116: occ = occupancy_u<1, 16>(deep, w); break;
-    case 208: occ = occupancy_u<2, 8>(deep, w); break;
-    case 216: occ = occupancy_u<2, 16>(deep, w); break;
-    case 408: occ = occupancy_u<4, 8>(deep, w); break;
-    default: break;
-  }
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    cus = 0;
-  const int slots = occ > 0 && cus > 0 ? occ * cus : 0;
-  cache[key] = slots;
-  return slots;
+  return cache[{dev, key}] = value();
+}
+// Resident workgroups of a kernel on `dev`: `occ()`, its workgroups per CU,
+// times the CU count (0: unknown).
+template <class F>
+int memo_slots(int dev, int key, F occ) {
+  return (int)dev_memo(dev, key, [&]() -> int64_t {
+    const int per_cu = occ();
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      cus = 0;
+    return per_cu > 0 && cus > 0 ? per_cu * cus : 0;
+  });
+}
+
+// ... of the reduce kernel (U, B, deep, weighted) (0 -> the plain table).
+int kernel_slots(int dev, int u, int b, bool deep, bool w) {
+  return memo_slots(dev, kMemoReduce + ((u * 32 + b) * 2 + deep) * 2 + w, [&] {
+    switch (u * 100 + b) {
+      case 108: return occupancy_u<1, 8>(deep, w);
+      case 116: return occupancy_u<1, 16>(deep, w);
+      case 208: return occupancy_u<2, 8>(deep, w);
+      case 216: return occupancy_u<2, 16>(deep, w);
+      case 408: return occupancy_u<4, 8>(deep, w);
+      default: return 0;
+    }
+  });
+}
+
+// ... of tgpu_kernel<0> (the fp32 torch-GPU order's S = 1 group's launch).
+int tgpu_slots(int dev, int batch) {
+  return memo_slots(dev, kMemoTgpu + (batch == 8), [&] {
+    int occ = 0;
+    const hipError_t e =
+        batch == 8 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tgpu_kernel<0, 8, 1>, kBlock, 0)
+                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tgpu_kernel<0, 16, 1>, kBlock, 0);
+    return e == hipSuccess ? occ : 0;
+  });
+}
+
+// ... of the 16-bit S = 1 group's kernel (fedagg_tgpu16.hip), by element
+// type and store width.
+int tgpu16_slots(int dev, int elem, bool wide) {
+  return memo_slots(dev, kMemoTgpu16 + elem * 2 + wide,
+                    [&] { return fa_tgpu16::occupancy_s1(elem, wide); });
+}
+
+// The dynamic LDS the S = 2 launch reserves (and never uses) so that at most
+// kTgpuS2Resident of its workgroups share a CU.  Measured r05
+// (profiles/r05_ab_lib_tgpu_s2.jsonl, same process) on the kernel before its
+// S = 4 riders (100 VGPRs, five per CU): three per CU 3-4 % faster than five,
+// two 10 % slower (a reservation of exactly a third of the CU's LDS admitted
+// only two: the allocation rounds up).  With the riders' paths it holds 130
+// VGPRs, three per CU by itself; the reservation keeps the measured count if
+// that changes.  The default reduce's 8-client kernels capped the same way
+// ran 20-25 % slower (r05_ab_lib_occupancy_cap.jsonl).  0 when the device
+// cannot say.
+#ifndef FA_TGPU_S2_RESIDENT
+#define FA_TGPU_S2_RESIDENT 3
+#endif
+constexpr int kTgpuS2Resident = FA_TGPU_S2_RESIDENT;
+size_t tgpu_s2_lds(int dev) {
+  return (size_t)dev_memo(dev, kMemoS2Lds, [&]() -> int64_t {
+    int per_cu = 0;
+    if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) !=
+        hipSuccess)
+      per_cu = 0;
+    // per_cu / (resident + 1/2): the allocation granularity may round the
+    // request up, and per_cu / resident exactly would then admit one fewer
+    return per_cu > 0 ? (2 * (int64_t)per_cu / (2 * kTgpuS2Resident + 1)) & ~(int64_t)1023 : 0;
+  });
 }
 
 hipError_t launch_chain(const ReduceArgs& a, int ntiles, int vec_u, hipStream_t st) {
@@ -1017,15 +1082,23 @@ hipError_t table_fill(void* dst, const std::vector<char>& host, hipStream_t st) 
 }  // namespace
 
 namespace {
+// Free a plan's device tables and the plan itself (fa_plan_destroy, and
+// PlanPtr below): the first hipFree error; every table is freed all the same.
+hipError_t plan_free(fa_plan* p) {
+  hipError_t first = hipSuccess;
+  std::vector<void*> tabs = {p->d_fac, p->d_tiles, p->d_tiles_alt, p->d_sidx};
+  tabs.insert(tabs.end(), p->d_bal.begin(), p->d_bal.end());
+  for (void* d : tabs) {
+    const hipError_t e = d ? hipFree(d) : hipSuccess;
+    if (first == hipSuccess) first = e;
+  }
+  delete p;
+  return first;
+}
 // A plan under construction: every error path frees whatever was uploaded;
 // a create path releases it into *out only on success.
 struct PlanDelete {
-  void operator()(fa_plan* p) const {
-    for (void* d : {(void*)p->d_fac, (void*)p->d_tiles, (void*)p->d_tiles_alt, (void*)p->d_sidx})
-      if (d) (void)hipFree(d);
-    for (Tile* d : p->d_bal) (void)hipFree(d);
-    delete p;
-  }
+  void operator()(fa_plan* p) const { (void)plan_free(p); }
 };
 using PlanPtr = std::unique_ptr<fa_plan, PlanDelete>;
 
@@ -1061,39 +1134,60 @@ hipError_t upload_tables(fa_plan* p, const std::vector<Tile>& tiles,
   return e;
 }
 
-// One body behind fa_plan_create, fa_plan_create_elem and
-// fa_plan_create_elem_out (`who`, in the messages).  A 16-bit plan (elem
+// What a plan entry point asks for: every segment-list entry fills one and
+// hands it to plan_from_segs.
+struct PlanSpec {
+  const char* who;         // the entry's name in the messages
+  const char* flags_hint;  // the tail of its unknown-flag message
+  const fa_seg* seg32; int nseg32; int64_t f32_numel;  // the floating bucket
+  const fa_seg* seg64; int nseg64; int64_t i64_numel;  // the int64 bucket
+  int tile_elems;  // the CPU order only (0 from the _order entries)
+  unsigned flags;
+  int n, order;    // the _order entries only
+  int elem, out_elem;
+};
+
+// The result bucket's type is the clients', or FA_ELEM_F32 over 16-bit
+// clients (a mixed plan: the fp32 master global).
+int check_elems(const char* who, int elem, int out_elem) {
+  if ((elem == FA_ELEM_F16 || elem == FA_ELEM_BF16) &&
+      (out_elem == elem || out_elem == FA_ELEM_F32))
+    return FA_OK;
+  return set_err(FA_E_INVAL, "%s: out_elem must equal elem, or be FA_ELEM_F32 over FA_ELEM_F16 / "
+                             "FA_ELEM_BF16 clients (got elem %d, out_elem %d)", who, elem, out_elem);
+}
+
+// The CPU-order body (fa_plan_create, _elem, _elem_out).  A 16-bit plan (elem
 // FA_ELEM_F16 / FA_ELEM_BF16) holds the plain table only, cut at 16-B
 // vectors of 8 elements; a mixed plan (out_elem FA_ELEM_F32 over 16-bit
 // clients) is that table, reduced by the wide-store instances of the 16-bit
 // kernels into an fp32 bucket at the same element offsets and broadcast by
 // the narrowing kernel.
-int plan_create(const char* who, const char* flags_hint, const fa_seg* seg32, int nseg32,
-                int64_t f32_numel, const fa_seg* seg64, int nseg64, int64_t i64_numel,
-                int tile_elems, unsigned flags, int elem, int out_elem, fa_plan** out) {
-  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
+int plan_create_cpu(const PlanSpec& s, fa_plan** out) {
+  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", s.who);
   *out = nullptr;
   fa_host::Layout l;
-  int rc = fa_host::parse_layout(who, flags_hint, fa_host::kCheckSizes | fa_host::kCheckTile, seg32,
-                                 nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
-                                 elem, &l);
+  int rc = fa_host::parse_layout(s.who, s.flags_hint, fa_host::kCheckSizes | fa_host::kCheckTile,
+                                 s.seg32, s.nseg32, s.f32_numel, s.seg64, s.nseg64, s.i64_numel,
+                                 s.tile_elems, s.flags, s.elem, &l);
   if (rc) return rc;
-  const bool h16 = elem != FA_ELEM_F32;
+  const bool h16 = s.elem != FA_ELEM_F32;
   PlanPtr p(new fa_plan());
-  p->elem = elem;
-  p->out_elem = out_elem;
+  p->family = h16 ? FaFamily::kH16 : FaFamily::kDefault;
+  p->elem = s.elem;
+  p->out_elem = s.out_elem;
   p->info = l.info;
   p->vec_u = l.info.tile_elems / (h16 ? fa_h16::kTile : 4 * kBlock);
   // a 16-bit plan: the plain table is the one launched
-  p->flags = h16 ? flags | FA_PLAN_TUNE_NO_BALANCE : flags;
-  p->flat_bcast = fa_host::flat_bcast_ok(flags, l, elem, out_elem);
+  p->flags = h16 ? s.flags | FA_PLAN_TUNE_NO_BALANCE : s.flags;
+  p->flat_bcast = fa_host::flat_bcast_ok(s.flags, l, s.elem, s.out_elem);
   std::vector<Tile> tiles, alt;
-  rc = fa_host::build_tiles(l.s32, l.s64, l.info.tile_elems, flags, &tiles, &p->info, l.valign);
+  rc = fa_host::build_tiles(l.s32, l.s64, l.info.tile_elems, s.flags, &tiles, &p->info, l.valign);
   if (rc) return rc;
   set_kinds(p.get(), tiles);
   if (l.autosel) {
     fa_plan_info ia{};
-    rc = fa_host::build_tiles(l.s32, l.s64, 4 * kBlock, flags, &alt, &ia);
+    rc = fa_host::build_tiles(l.s32, l.s64, 4 * kBlock, s.flags, &alt, &ia);
     if (rc) return rc;
   }
   hipError_t e = hipGetDevice(&p->device);
@@ -1103,6 +1197,107 @@ int plan_create(const char* who, const char* flags_hint, const fa_seg* seg32, in
                    hipGetErrorString(e));
   *out = p.release();
   return FA_OK;
+}
+
+// The torch-GPU-order body (fa_plan_create_order, _order_elem,
+// _order_elem_out).  Two arms, each with the checks of the entry it came
+// from in that entry's order.  fp32: order, n, the segments (no size or tile
+// check; 1024-float tiles), then the device is asked for tgpu_kernel<0>'s
+// slots.  16-bit: the table fa_plan_build_order_host_elem returns for the
+// clients' type (fa_host::plan_order_elem: order, n, elem, sizes, segments),
+// with a result bucket of that type or (out_elem FA_ELEM_F32) an fp32 one at
+// the same element offsets; the slots of its S = 1 kernel are asked before
+// those checks, and only for an element type that has a kernel.
+int plan_create_tgpu(const PlanSpec& s, fa_plan** out) {
+  int rc = fa_host::check_flags(s.who, s.flags);
+  if (rc) return rc;
+  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", s.who);
+  *out = nullptr;
+  const bool h16 = s.elem != FA_ELEM_F32;
+  const bool balance = !(s.flags & FA_PLAN_TUNE_NO_BALANCE);
+  fa_host::Layout l;
+  fa_host::TgpuTables t;
+  int dev = 0;
+  hipError_t e;
+  if (h16) {
+    e = hipGetDevice(&dev);
+    const bool known = s.elem == FA_ELEM_F16 || s.elem == FA_ELEM_BF16;
+    const int slots = e == hipSuccess && known && balance
+                          ? tgpu16_slots(dev, s.elem, s.out_elem != s.elem)
+                          : 0;
+    rc = fa_host::plan_order_elem(s.who, s.seg32, s.nseg32, s.f32_numel, s.seg64, s.nseg64,
+                                  s.i64_numel, s.n, s.order, s.flags, s.elem, slots, &l, &t);
+  } else {
+    if (s.order != FA_ORDER_TORCH_GPU)
+      return set_err(FA_E_INVAL, "%s: order %d", s.who, s.order);
+    if (s.n < 2 || s.n > FA_MAX_CLIENTS)
+      return set_err(FA_E_RANGE, "%s: n=%d outside 2..%d", s.who, s.n, FA_MAX_CLIENTS);
+    rc = fa_host::parse_layout(s.who, "", 0, s.seg32, s.nseg32, s.f32_numel, s.seg64, s.nseg64,
+                               s.i64_numel, 4 * kBlock, s.flags, FA_ELEM_F32, &l);
+    if (rc) return rc;
+    e = hipGetDevice(&dev);
+    const int slots =
+        e == hipSuccess && balance ? tgpu_slots(dev, fa_host::tgpu_batch_for(s.n)) : 0;
+    rc = fa_host::plan_tgpu(l.s32, l.s64, s.n, s.flags, slots, &t);
+  }
+  if (rc) return rc;
+  PlanPtr p(new fa_plan());
+  p->family = h16 ? FaFamily::kTgpu16 : FaFamily::kTgpu;
+  for (int g = 0; g < 6; ++g) p->tg_lo[g] = t.lo[g];
+  p->info = l.info;
+  p->info.ntiles = (int32_t)t.tiles.size();
+  p->info.ntiles_tail = (int32_t)t.tiles.size();
+  p->flags = s.flags;
+  p->elem = s.elem;
+  p->out_elem = s.out_elem;
+  p->flat_bcast = fa_host::flat_bcast_ok(s.flags, l, s.elem, s.out_elem);
+  p->order_n = s.n;
+  set_kinds(p.get(), t.tiles);
+  p->device = dev;
+  if (h16) {
+    // (no LDS reservation on the S = 2 launch: tgpu_s2_lds was measured on
+    // the fp32 instance only)
+    p->vec_u = 1;
+  } else {
+    p->tgpu_batch = fa_host::tgpu_batch_for(s.n);
+    if (e == hipSuccess) p->tgpu_s2_lds = tgpu_s2_lds(dev);
+  }
+  if (e == hipSuccess) e = upload(&p->d_tiles, t.tiles);
+  if (e == hipSuccess) e = upload(&p->d_fac, t.fac);
+  if (e != hipSuccess) return set_err(FA_E_HIP, "%s: %s", s.who, hipGetErrorString(e));
+  *out = p.release();
+  return FA_OK;
+}
+
+// The forwarding rules of the six segment-list entries, in one place.  A
+// call is named, in every message, by what it asks for and not by the symbol
+// it came through: FA_ELEM_F32 drops "_elem", out_elem == elem drops "_out",
+// FA_ORDER_TORCH_CPU drops "_order" — an _elem entry given FA_ELEM_F32 is
+// the plain entry, an _elem_out entry with out_elem == elem the _elem entry,
+// an _order* entry with the CPU order the entry without the order (DESIGN
+// §3.1 has the table).  One trace of the symbol stays: fa_plan_create_order
+// checks the flag bits under its own name before it forwards the CPU order
+// (`order_entry`: the call came through an _order* symbol).
+int plan_from_segs(PlanSpec s, bool order_entry, fa_plan** out) {
+  static const char* const kWho[2][3] = {
+      {"fa_plan_create", "fa_plan_create_elem", "fa_plan_create_elem_out"},
+      {"fa_plan_create_order", "fa_plan_create_order_elem", "fa_plan_create_order_elem_out"}};
+  const bool tgpu = s.order != FA_ORDER_TORCH_CPU;
+  const bool h16 = s.elem != FA_ELEM_F32, mixed = s.out_elem != s.elem;
+  const bool plain = !h16 && !mixed;
+  if (order_entry && plain) {
+    const int rc = fa_host::check_flags(kWho[1][0], s.flags);
+    if (rc) return rc;
+  }
+  s.who = kWho[tgpu][mixed ? 2 : h16];
+  s.flags_hint = plain && !tgpu ? " (removed tuning flags?)" : "";
+  if (mixed) {
+    if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", s.who);
+    *out = nullptr;
+    const int rc = check_elems(s.who, s.elem, s.out_elem);
+    if (rc) return rc;
+  }
+  return tgpu ? plan_create_tgpu(s, out) : plan_create_cpu(s, out);
 }
 }  // namespace
 
@@ -1114,34 +1309,50 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 int fa_plan_create(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
                    int nseg64, int64_t i64_numel, int tile_elems, unsigned flags,
                    fa_plan** out) {
-  return plan_create("fa_plan_create", " (removed tuning flags?)", seg32, nseg32, f32_numel, seg64,
-                     nseg64, i64_numel, tile_elems, flags, FA_ELEM_F32, FA_ELEM_F32, out);
+  return plan_from_segs({nullptr, nullptr, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel,
+                         tile_elems, flags, 0, FA_ORDER_TORCH_CPU, FA_ELEM_F32, FA_ELEM_F32},
+                        false, out);
 }
 
 int fa_plan_create_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
                         int nseg64, int64_t i64_numel, int tile_elems, unsigned flags, int elem,
                         fa_plan** out) {
-  if (elem == FA_ELEM_F32)
-    return fa_plan_create(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems, flags,
-                          out);
-  return plan_create("fa_plan_create_elem", "", seg32, nseg32, f32_numel, seg64, nseg64, i64_numel,
-                     tile_elems, flags, elem, elem, out);
+  return plan_from_segs({nullptr, nullptr, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel,
+                         tile_elems, flags, 0, FA_ORDER_TORCH_CPU, elem, elem},
+                        false, out);
 }
 
 int fa_plan_create_elem_out(const fa_seg* seg32, int nseg32, int64_t f32_numel,
                             const fa_seg* seg64, int nseg64, int64_t i64_numel, int tile_elems,
                             unsigned flags, int elem, int out_elem, fa_plan** out) {
-  if (out_elem == elem)
-    return fa_plan_create_elem(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, tile_elems,
-                               flags, elem, out);
-  if (!out) return set_err(FA_E_INVAL, "fa_plan_create_elem_out: out is NULL");
-  *out = nullptr;
-  if (!((elem == FA_ELEM_F16 || elem == FA_ELEM_BF16) && out_elem == FA_ELEM_F32))
-    return set_err(FA_E_INVAL, "fa_plan_create_elem_out: out_elem must equal elem, or be "
-                               "FA_ELEM_F32 over FA_ELEM_F16 / FA_ELEM_BF16 clients (got elem %d, "
-                               "out_elem %d)", elem, out_elem);
-  return plan_create("fa_plan_create_elem_out", "", seg32, nseg32, f32_numel, seg64, nseg64,
-                     i64_numel, tile_elems, flags, elem, out_elem, out);
+  return plan_from_segs({nullptr, nullptr, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel,
+                         tile_elems, flags, 0, FA_ORDER_TORCH_CPU, elem, out_elem},
+                        false, out);
+}
+
+int fa_plan_create_order(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
+                         int nseg64, int64_t i64_numel, int n, int order, unsigned flags,
+                         fa_plan** out) {
+  return plan_from_segs({nullptr, nullptr, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0,
+                         flags, n, order, FA_ELEM_F32, FA_ELEM_F32},
+                        true, out);
+}
+
+int fa_plan_create_order_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                              const fa_seg* seg64, int nseg64, int64_t i64_numel, int n, int order,
+                              unsigned flags, int elem, fa_plan** out) {
+  return plan_from_segs({nullptr, nullptr, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0,
+                         flags, n, order, elem, elem},
+                        true, out);
+}
+
+int fa_plan_create_order_elem_out(const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                                  const fa_seg* seg64, int nseg64, int64_t i64_numel, int n,
+                                  int order, unsigned flags, int elem, int out_elem,
+                                  fa_plan** out) {
+  return plan_from_segs({nullptr, nullptr, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0,
+                         flags, n, order, elem, out_elem},
+                        true, out);
 }
 
 int fa_plan_elem(const fa_plan* plan) {
@@ -1152,208 +1363,6 @@ int fa_plan_elem(const fa_plan* plan) {
 int fa_plan_out_elem(const fa_plan* plan) {
   if (!plan) return set_err(FA_E_INVAL, "fa_plan_out_elem: plan is NULL");
   return plan->out_elem;
-}
-
-namespace {
-// Resident workgroups of tgpu_kernel<0> (the S = 1 group's launch) on `dev`,
-// queried once per process (0: unknown).
-int tgpu_slots(int dev, int batch) {
-  static std::mutex mu;
-  static std::map<int, int> cache;
-  std::lock_guard<std::mutex> lk(mu);
-  const int key = dev * 2 + (batch == 8);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int occ = 0, cus = 0;
-  const hipError_t e =
-      batch == 8 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tgpu_kernel<0, 8, 1>, kBlock, 0)
-                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tgpu_kernel<0, 16, 1>, kBlock, 0);
-  if (e != hipSuccess) occ = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    cus = 0;
-  return cache[key] = occ > 0 && cus > 0 ? occ * cus : 0;
-}
-
-// The dynamic LDS the S = 2 launch reserves (and never uses) so that at most
-// kTgpuS2Resident of its workgroups share a CU.  Measured r05
-// (profiles/r05_ab_lib_tgpu_s2.jsonl, same process) on the kernel before its
-// S = 4 riders (100 VGPRs, five per CU): three per CU 3-4 % faster than five,
-// two 10 % slower (a reservation of exactly a third of the CU's LDS admitted
-// only two: the allocation rounds up).  With the riders' paths it holds 130
-// VGPRs, three per CU by itself; the reservation keeps the measured count if
-// that changes.  The default reduce's 8-client kernels capped the same way
-// ran 20-25 % slower (r05_ab_lib_occupancy_cap.jsonl).  0 when the device
-// cannot say.
-#ifndef FA_TGPU_S2_RESIDENT
-#define FA_TGPU_S2_RESIDENT 3
-#endif
-constexpr int kTgpuS2Resident = FA_TGPU_S2_RESIDENT;
-size_t tgpu_s2_lds(int dev) {
-  static std::mutex mu;
-  static std::map<int, size_t> cache;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int per_cu = 0;
-  if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) !=
-      hipSuccess)
-    per_cu = 0;
-  // per_cu / (resident + 1/2): the allocation granularity may round the
-  // request up, and per_cu / resident exactly would then admit one fewer
-  return cache[dev] =
-             per_cu > 0 ? (size_t)(2 * (int64_t)per_cu / (2 * kTgpuS2Resident + 1)) & ~(size_t)1023
-                        : 0;
-}
-
-}  // namespace
-
-int fa_plan_create_order(const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
-                         int nseg64, int64_t i64_numel, int n, int order, unsigned flags,
-                         fa_plan** out) {
-  int rc = fa_host::check_flags("fa_plan_create_order", flags);
-  if (rc) return rc;
-  if (order == FA_ORDER_TORCH_CPU)
-    return fa_plan_create(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags, out);
-  if (!out) return set_err(FA_E_INVAL, "fa_plan_create_order: out is NULL");
-  *out = nullptr;
-  if (order != FA_ORDER_TORCH_GPU)
-    return set_err(FA_E_INVAL, "fa_plan_create_order: order %d", order);
-  if (n < 2 || n > FA_MAX_CLIENTS)
-    return set_err(FA_E_RANGE, "fa_plan_create_order: n=%d outside 2..%d", n, FA_MAX_CLIENTS);
-  fa_host::Layout l;
-  rc = fa_host::parse_layout("fa_plan_create_order", "", 0, seg32, nseg32, f32_numel, seg64,
-                             nseg64, i64_numel, 4 * kBlock, flags, FA_ELEM_F32, &l);
-  if (rc) return rc;
-  // the planner's one device input: the S = 1 launch's resident workgroups
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  const int slots = e == hipSuccess && !(flags & FA_PLAN_TUNE_NO_BALANCE)
-                        ? tgpu_slots(dev, fa_host::tgpu_batch_for(n))
-                        : 0;
-  fa_host::TgpuTables t;
-  rc = fa_host::plan_tgpu(l.s32, l.s64, n, flags, slots, &t);
-  if (rc) return rc;
-  PlanPtr p(new fa_plan());
-  for (int g = 0; g < 6; ++g) p->tg_lo[g] = t.lo[g];
-  p->info = l.info;
-  p->info.ntiles = (int32_t)t.tiles.size();
-  p->info.ntiles_tail = (int32_t)t.tiles.size();
-  p->flags = flags;
-  p->flat_bcast = fa_host::flat_bcast_ok(flags, l, FA_ELEM_F32, FA_ELEM_F32);
-  p->order = FA_ORDER_TORCH_GPU;
-  p->order_n = n;
-  p->tgpu_batch = fa_host::tgpu_batch_for(n);
-  set_kinds(p.get(), t.tiles);
-  p->device = dev;
-  if (e == hipSuccess) p->tgpu_s2_lds = tgpu_s2_lds(dev);
-  if (e == hipSuccess) e = upload(&p->d_tiles, t.tiles);
-  if (e == hipSuccess) e = upload(&p->d_fac, t.fac);
-  if (e != hipSuccess)
-    return set_err(FA_E_HIP, "fa_plan_create_order: %s", hipGetErrorString(e));
-  *out = p.release();
-  return FA_OK;
-}
-
-namespace {
-// Resident workgroups of the 16-bit S = 1 group's kernel (fedagg_tgpu16.hip)
-// on `dev`, queried once per process, element type and store width (0:
-// unknown).
-int tgpu16_slots(int dev, int elem, bool wide) {
-  static std::mutex mu;
-  static std::map<int, int> cache;
-  std::lock_guard<std::mutex> lk(mu);
-  const int key = (dev * 4 + elem) * 2 + wide;
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int cus = 0;
-  const int occ = fa_tgpu16::occupancy_s1(elem, wide);
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    cus = 0;
-  return cache[key] = occ > 0 && cus > 0 ? occ * cus : 0;
-}
-
-// One body behind the torch-GPU-order arms of fa_plan_create_order_elem and
-// fa_plan_create_order_elem_out (`who`, in the messages): the table
-// fa_plan_build_order_host_elem returns for the clients' 16-bit type, with a
-// result bucket of that type or (out_elem FA_ELEM_F32) an fp32 one at the
-// same element offsets.
-int order_elem_plan(const char* who, const fa_seg* seg32, int nseg32, int64_t f32_numel,
-                    const fa_seg* seg64, int nseg64, int64_t i64_numel, int n, int order,
-                    unsigned flags, int elem, int out_elem, fa_plan** out) {
-  int rc = fa_host::check_flags(who, flags);
-  if (rc) return rc;
-  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
-  *out = nullptr;
-  // the planner's one device input: the S = 1 launch's resident workgroups
-  // (asked only for an element type that has a kernel; the checks below
-  // refuse every other)
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  const bool known = elem == FA_ELEM_F16 || elem == FA_ELEM_BF16;
-  const int slots = e == hipSuccess && known && !(flags & FA_PLAN_TUNE_NO_BALANCE)
-                        ? tgpu16_slots(dev, elem, out_elem != elem)
-                        : 0;
-  fa_host::Layout l;
-  fa_host::TgpuTables t;
-  rc = fa_host::plan_order_elem(who, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order,
-                                flags, elem, slots, &l, &t);
-  if (rc) return rc;
-  PlanPtr p(new fa_plan());
-  for (int g = 0; g < 6; ++g) p->tg_lo[g] = t.lo[g];
-  p->info = l.info;
-  p->info.ntiles = (int32_t)t.tiles.size();
-  p->info.ntiles_tail = (int32_t)t.tiles.size();
-  p->flags = flags;
-  p->elem = elem;
-  p->out_elem = out_elem;
-  p->vec_u = 1;
-  p->flat_bcast = fa_host::flat_bcast_ok(flags, l, elem, out_elem);
-  p->order = FA_ORDER_TORCH_GPU;
-  p->order_n = n;
-  set_kinds(p.get(), t.tiles);
-  p->device = dev;
-  // (no LDS reservation on the S = 2 launch: tgpu_s2_lds was measured on the
-  // fp32 instance only)
-  if (e == hipSuccess) e = upload(&p->d_tiles, t.tiles);
-  if (e == hipSuccess) e = upload(&p->d_fac, t.fac);
-  if (e != hipSuccess) return set_err(FA_E_HIP, "%s: %s", who, hipGetErrorString(e));
-  *out = p.release();
-  return FA_OK;
-}
-}  // namespace
-
-int fa_plan_create_order_elem(const fa_seg* seg32, int nseg32, int64_t f32_numel,
-                              const fa_seg* seg64, int nseg64, int64_t i64_numel, int n, int order,
-                              unsigned flags, int elem, fa_plan** out) {
-  if (elem == FA_ELEM_F32)
-    return fa_plan_create_order(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order,
-                                flags, out);
-  if (order == FA_ORDER_TORCH_CPU)
-    return fa_plan_create_elem(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags, elem,
-                               out);
-  return order_elem_plan("fa_plan_create_order_elem", seg32, nseg32, f32_numel, seg64, nseg64,
-                         i64_numel, n, order, flags, elem, elem, out);
-}
-
-int fa_plan_create_order_elem_out(const fa_seg* seg32, int nseg32, int64_t f32_numel,
-                                  const fa_seg* seg64, int nseg64, int64_t i64_numel, int n,
-                                  int order, unsigned flags, int elem, int out_elem,
-                                  fa_plan** out) {
-  if (out_elem == elem)
-    return fa_plan_create_order_elem(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order,
-                                     flags, elem, out);
-  if (order == FA_ORDER_TORCH_CPU)
-    return fa_plan_create_elem_out(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags,
-                                   elem, out_elem, out);
-  const char* who = "fa_plan_create_order_elem_out";
-  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
-  *out = nullptr;
-  if (!((elem == FA_ELEM_F16 || elem == FA_ELEM_BF16) && out_elem == FA_ELEM_F32))
-    return set_err(FA_E_INVAL, "%s: out_elem must equal elem, or be FA_ELEM_F32 over FA_ELEM_F16 / "
-                               "FA_ELEM_BF16 clients (got elem %d, out_elem %d)", who, elem,
-                   out_elem);
-  return order_elem_plan(who, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, n, order, flags,
-                         elem, out_elem, out);
 }
 
 namespace {
@@ -1416,6 +1425,7 @@ int plan_from_tiles(const char* who, const fa_tile_desc* tiles, int ntiles, int6
   in.ntiles_cascade = (int32_t)vec.size();
   in.ntiles_tail = (int32_t)sc.size();
   PlanPtr p(new fa_plan());
+  p->family = h16 ? FaFamily::kH16 : FaFamily::kDefault;
   p->info = in;
   p->elem = elem;
   p->out_elem = out_elem;
@@ -1442,25 +1452,19 @@ int fa_plan_create_from_tiles_elem(const fa_tile_desc* tiles, int ntiles, int64_
                                    int out_elem, fa_plan** out) {
   if (elem == FA_ELEM_F32 && out_elem == FA_ELEM_F32)
     return fa_plan_create_from_tiles(tiles, ntiles, f32_numel, i64_numel, tile_elems, flags, out);
-  if (!out) return set_err(FA_E_INVAL, "fa_plan_create_from_tiles_elem: out is NULL");
+  const char* who = "fa_plan_create_from_tiles_elem";
+  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
   *out = nullptr;
-  if (!((elem == FA_ELEM_F16 || elem == FA_ELEM_BF16) &&
-        (out_elem == elem || out_elem == FA_ELEM_F32)))
-    return set_err(FA_E_INVAL, "fa_plan_create_from_tiles_elem: out_elem must equal elem, or be "
-                               "FA_ELEM_F32 over FA_ELEM_F16 / FA_ELEM_BF16 clients (got elem %d, "
-                               "out_elem %d)", elem, out_elem);
-  return plan_from_tiles("fa_plan_create_from_tiles_elem", tiles, ntiles, f32_numel, i64_numel,
-                         tile_elems, flags, elem, out_elem, out);
+  const int rc = check_elems(who, elem, out_elem);
+  if (rc) return rc;
+  return plan_from_tiles(who, tiles, ntiles, f32_numel, i64_numel, tile_elems, flags, elem, out_elem,
+                         out);
 }
 
 int fa_plan_destroy(fa_plan* plan) {
   if (!plan) return FA_OK;
-  if (plan->d_fac) HIP_TRY(hipFree(plan->d_fac));
-  if (plan->d_tiles) HIP_TRY(hipFree(plan->d_tiles));
-  if (plan->d_tiles_alt) HIP_TRY(hipFree(plan->d_tiles_alt));
-  if (plan->d_sidx) HIP_TRY(hipFree(plan->d_sidx));
-  for (Tile* d : plan->d_bal) HIP_TRY(hipFree(d));
-  delete plan;
+  const hipError_t e = plan_free(plan);
+  if (e != hipSuccess) return set_err(FA_E_HIP, "fa_plan_destroy: hipFree: %s", hipGetErrorString(e));
   return FA_OK;
 }
 
@@ -1522,21 +1526,19 @@ hipError_t launch_bcast(const fa_plan* plan, ReduceArgs& a, int n, int ntiles, h
 int fa_plan_launch_shape(const fa_plan* plan, int n, int weighted, int* ntiles, int* slots) {
   if (!plan || !ntiles || !slots || n < 1)
     return set_err(FA_E_INVAL, "fa_plan_launch_shape: bad arguments");
-  if (plan->order == FA_ORDER_TORCH_GPU) {
-    *ntiles = plan->info.ntiles;
-    *slots = 0;
-    return FA_OK;
+  *slots = 0;
+  switch (plan->family) {
+    case FaFamily::kTgpu:
+    case FaFamily::kTgpu16: *ntiles = plan->info.ntiles; break;
+    case FaFamily::kH16: *ntiles = plan->nt; break;  // one table, launched as it is
+    case FaFamily::kDefault: {
+      const fa_host::Launch L = fa_host::select_launch(*plan, n, weighted != 0, kernel_slots);
+      *ntiles = L.nt;
+      *slots = L.slots ? L.slots
+                       : fa_host::call_slots(plan->device, n, L.vec_u, weighted != 0,
+                                             plan->flags & ~FA_PLAN_TUNE_NO_BALANCE, kernel_slots);
+    }
   }
-  if (plan->elem != FA_ELEM_F32) {  // one table, launched as it is
-    *ntiles = plan->nt;
-    *slots = 0;
-    return FA_OK;
-  }
-  const fa_host::Launch L = fa_host::select_launch(*plan, n, weighted != 0, kernel_slots);
-  *ntiles = L.nt;
-  *slots = L.slots ? L.slots
-                   : fa_host::call_slots(plan->device, n, L.vec_u, weighted != 0,
-                                         plan->flags & ~FA_PLAN_TUNE_NO_BALANCE, kernel_slots);
   return FA_OK;
 }
 
@@ -1544,22 +1546,20 @@ int fa_plan_launch_form(const fa_plan* plan, int n, int weighted, int* tile_elem
                         int* pipe) {
   if (!plan || !tile_elems || !batch || !pipe || n < 1)
     return set_err(FA_E_INVAL, "fa_plan_launch_form: bad arguments");
-  if (plan->order == FA_ORDER_TORCH_GPU) {
-    *tile_elems = 0;
-    *batch = 0;
-    *pipe = 0;
-    return FA_OK;
+  switch (plan->family) {
+    case FaFamily::kTgpu:
+    case FaFamily::kTgpu16: *tile_elems = *batch = *pipe = 0; break;
+    case FaFamily::kH16:  // the client loop, one client per step
+      *tile_elems = plan->info.tile_elems;
+      *batch = *pipe = 1;
+      break;
+    case FaFamily::kDefault: {
+      const fa_host::Launch L = fa_host::select_launch(*plan, n, weighted != 0, kernel_slots);
+      *tile_elems = 4 * kBlock * L.vec_u;
+      *batch = L.batch;
+      *pipe = L.pipe;
+    }
   }
-  if (plan->elem != FA_ELEM_F32) {  // the client loop, one client per step
-    *tile_elems = plan->info.tile_elems;
-    *batch = 1;
-    *pipe = 1;
-    return FA_OK;
-  }
-  const fa_host::Launch L = fa_host::select_launch(*plan, n, weighted != 0, kernel_slots);
-  *tile_elems = 4 * kBlock * L.vec_u;
-  *batch = L.batch;
-  *pipe = L.pipe;
   return FA_OK;
 }
 
@@ -1629,16 +1629,21 @@ struct ClientTable {
 // the broadcast alone (the reference's initial sync, train_fedavg.py:
 // 244-250, and :148-149 without the reduce): out32/out64 -> every client
 hipError_t run_bcast_only(const fa_plan* plan, ReduceArgs& a, int n, hipStream_t st) {
-  const int nt = plan->order == FA_ORDER_TORCH_GPU ? plan->info.ntiles : plan->nt;
+  const int nt = plan->tgpu() ? plan->info.ntiles : plan->nt;
   a.ntiles = nt;
   a.sidx = plan->d_sidx;
   return launch_bcast(plan, a, n, nt, st);
 }
 
-// one launch per row-split group of the plan's table; the broadcast as its
-// own launch over the whole table, client groups per tile (as the default
-// order's split broadcast)
-hipError_t run_tgpu(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipStream_t st) {
+// A torch-GPU-order plan: one launch per row-split group of its table
+// (`launch(g, cnt)`, inlined: the per-round host path), then the broadcast
+// as its own launch over the whole table — client groups per tile (as the
+// default order's split broadcast); on a 16-bit plan the flat byte copy of
+// the result bucket (fa_reduce_tab has refused one without coverage) or, with
+// an fp32 result bucket, the narrowing broadcast.
+extern "C++" template <class LaunchGroup>
+hipError_t run_groups(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipStream_t st,
+                      LaunchGroup launch) {
   hipError_t e = hipSuccess;
   for (int g = 0; g < 5 && e == hipSuccess; ++g) {
     const int lo = plan->tg_lo[g], cnt = plan->tg_lo[g + 1] - lo;
@@ -1646,6 +1651,18 @@ hipError_t run_tgpu(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipSt
     a.tiles = plan->d_tiles + lo;
     a.tfac = plan->d_fac + lo;
     a.ntiles = cnt;
+    e = launch(g, cnt);
+  }
+  if (e == hipSuccess && bcast && plan->tg_lo[5] > 0) {
+    a.tiles = plan->d_tiles;
+    a.ntiles = plan->tg_lo[5];
+    e = launch_bcast(plan, a, n, a.ntiles, st);
+  }
+  return e;
+}
+
+hipError_t run_tgpu(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipStream_t st) {
+  return run_groups(plan, a, n, bcast, st, [&](int g, int cnt) {
     switch (g) {
       case 0:
         // the client loop on full tiles at every N (r05,
@@ -1662,37 +1679,16 @@ hipError_t run_tgpu(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipSt
       case 3: hipLaunchKernelGGL(tgpu_kernel<3>, dim3(cnt), dim3(kBlock), 0, st, a); break;
       default: hipLaunchKernelGGL(tgpu_kernel<4>, dim3(cnt), dim3(kBlock), 0, st, a); break;
     }
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && bcast && plan->tg_lo[5] > 0) {
-    a.tiles = plan->d_tiles;
-    a.ntiles = plan->tg_lo[5];
-    e = launch_bcast(plan, a, n, a.ntiles, st);
-  }
-  return e;
+    return hipGetLastError();
+  });
 }
 
-// a 16-bit torch-GPU-order plan (fa_plan_create_order_elem): one launch of
-// fedagg_tgpu16.hip's kernels per row-split group, then the flat byte copy
-// of the result bucket (fa_reduce_tab has refused a plan without coverage);
-// with an fp32 result bucket (fa_plan_create_order_elem_out) their wide-store
-// instances, then the narrowing broadcast
+// fedagg_tgpu16.hip's kernels; with an fp32 result bucket
+// (fa_plan_create_order_elem_out) their wide-store instances
 hipError_t run_tgpu16(const fa_plan* plan, ReduceArgs& a, int n, bool bcast, hipStream_t st) {
-  hipError_t e = hipSuccess;
-  for (int g = 0; g < 5 && e == hipSuccess; ++g) {
-    const int lo = plan->tg_lo[g], cnt = plan->tg_lo[g + 1] - lo;
-    if (cnt == 0) continue;
-    a.tiles = plan->d_tiles + lo;
-    a.tfac = plan->d_fac + lo;
-    a.ntiles = cnt;
-    e = fa_tgpu16::launch(a, g, cnt, plan->elem, plan->out_elem == FA_ELEM_F32, st);
-  }
-  if (e == hipSuccess && bcast && plan->tg_lo[5] > 0) {
-    a.tiles = plan->d_tiles;
-    a.ntiles = plan->tg_lo[5];
-    e = launch_bcast(plan, a, n, a.ntiles, st);
-  }
-  return e;
+  return run_groups(plan, a, n, bcast, st, [&](int g, int cnt) {
+    return fa_tgpu16::launch(a, g, cnt, plan->elem, plan->out_elem == FA_ELEM_F32, st);
+  });
 }
 
 // the 16-bit kernels (fedagg_h16.hip) over the plan's one table, then the
@@ -1732,7 +1728,7 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
     return set_err(FA_E_RANGE, "fa_reduce: n=%d exceeds FA_MAX_CLIENTS=%d", n, FA_MAX_CLIENTS);
   if (flags & ~(FA_F_BCAST | FA_F_SUM_ONLY | FA_F_BCAST_ONLY))
     return set_err(FA_E_INVAL, "fa_reduce: bad flags");
-  const bool tgpu = plan->order == FA_ORDER_TORCH_GPU;
+  const bool tgpu = plan->tgpu();
   if (tgpu && weights)
     return set_err(FA_E_INVAL, "fa_reduce: the torch-GPU order is the reference's unweighted mean");
   const bool h16 = plan->elem != FA_ELEM_F32;
@@ -1786,22 +1782,19 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
   hipError_t e = tab.fill(a, need32 ? c32 : nullptr, need64 ? c64 : nullptr, n, weights, ctable);
   if (e != hipSuccess)
     return set_err(FA_E_HIP, "fa_reduce: client pointer table: %s", hipGetErrorString(e));
-  const char* what;
+  static const char* const kWhat[] = {"reduce launch", "16-bit reduce launch",
+                                      "torch-GPU-order launch", "16-bit torch-GPU-order launch"};
+  const char* what = bcast_only ? "broadcast launch" : kWhat[(int)plan->family];
+  const bool w = weights != nullptr;
   if (bcast_only) {
-    what = "broadcast launch";
     e = run_bcast_only(plan, a, n, st);
-  } else if (tgpu && h16) {
-    what = "16-bit torch-GPU-order launch";
-    e = run_tgpu16(plan, a, n, bcast, st);
-  } else if (tgpu) {
-    what = "torch-GPU-order launch";
-    e = run_tgpu(plan, a, n, bcast, st);
-  } else if (h16) {
-    what = "16-bit reduce launch";
-    e = run_h16(plan, a, n, weights != nullptr, bcast, st);
   } else {
-    what = "reduce launch";
-    e = run_default(plan, a, n, weights != nullptr, bcast, st);
+    switch (plan->family) {
+      case FaFamily::kDefault: e = run_default(plan, a, n, w, bcast, st); break;
+      case FaFamily::kH16: e = run_h16(plan, a, n, w, bcast, st); break;
+      case FaFamily::kTgpu: e = run_tgpu(plan, a, n, bcast, st); break;
+      case FaFamily::kTgpu16: e = run_tgpu16(plan, a, n, bcast, st); break;
+    }
   }
   e = tab.done(e);
   if (e != hipSuccess) return set_err(FA_E_HIP, "%s: %s", what, hipGetErrorString(e));

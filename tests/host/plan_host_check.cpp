@@ -113,7 +113,7 @@ void check_cover(const std::string& name, const Segs& L, const std::vector<Tile>
 
 void run_default(const std::string& name, const Segs& L, int tile_elems, unsigned flags, int elem,
                  std::map<std::string, std::string>* out) {
-  // the host half of fedagg.hip plan_create
+  // the host half of fedagg.hip plan_create_cpu
   fa_host::Layout l;
   int rc = fa_host::parse_layout("check", "", fa_host::kCheckSizes | fa_host::kCheckTile,
                                  L.s32.data(), (int)L.s32.size(), L.f32_numel, L.s64.data(),
