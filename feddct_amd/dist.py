@@ -399,7 +399,8 @@ class StripedAggregator:
       each GPU uploads only ITS stripe of every client (no xGMI traffic for
       inputs; ingress bandwidth scales with the GPUs' PCIe links).
 
-    The result is the same bits as the single-GPU reduction (tested).
+    The result is the same bits as the single-GPU reduction (tested).  Only
+    the result ranks' ``out32`` / ``out64`` are written, the int64 keys too.
     """
 
     def __init__(self, layout: BucketLayout, n_total: int, out32: torch.Tensor,
@@ -450,7 +451,8 @@ class StripedAggregator:
         for j, t in enumerate(local64):
             self.stack64[j].copy_(t)
         dist.all_gather_into_tensor(self.gather64, self.stack64, group=self.group)
-        self.backend.reduce_i64([self.gather64[r] for r in self.rows64], self.out64)
+        if self.root < 0 or self.root == self.rank:   # out64 belongs to the result ranks
+            self.backend.reduce_i64([self.gather64[r] for r in self.rows64], self.out64)
 
     def schedule(self):
         """This rank's exchange steps, in issue order (``stripe_schedule``)."""
@@ -518,11 +520,11 @@ class StripedAggregator:
         for c, (lo, hi, _) in enumerate(self.chunks[self.rank]):
             if hi > lo:
                 self.backend.reduce_chunk(c, lo, hi, sources, dst)
-        if self.layout.i64_numel:
+        me, result = self.rank, self.root < 0 or self.root == self.rank
+        if self.layout.i64_numel and result:   # out64 belongs to the result ranks
             g = torch.stack([t.to(self.out64.device, non_blocking=True) for t in clients64])
             self.backend.reduce_i64(list(g.unbind(0)), self.out64)
         # the finished stripes to the result ranks, every peer in one batch
-        me, result = self.rank, self.root < 0 or self.root == self.rank
         post = []
         for q in range(1, self.world):
             r = (me + q) % self.world

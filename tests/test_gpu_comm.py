@@ -3,8 +3,12 @@
 the exchange is the identity, so the result must equal the single-GPU
 reduction bit for bit — which checks the chunking (every column summed once,
 padding-spanning exchanges), the /N finish on the comm stream, the int64
-gather + exact reduce and the stream joins.  The multi-rank orchestration is
-covered on CPU with gloo (tests/test_dist_gloo.py) and by bench.py --gpus N."""
+gather + exact reduce and the stream joins.  The multi-rank orchestration of
+feddct_amd/dist.py runs on CPU with gloo and the oracle backends
+(tests/test_dist_gloo.py, tests/test_multi_default.py) and on the GPU with its
+own HIP backends at W = 1, 2, 3 and 8 ranks over an in-process stand-in for
+torch.distributed (tests/test_gpu_dist_loopback.py); the native rounds at
+W = 2..8 in tests/test_gpu_loopback.py."""
 import ctypes
 
 import numpy as np
