@@ -14,6 +14,13 @@ ULP from the exact result (``E1_ULP_R04``).  torch.distributed only carries
 the communicator's 128-byte id from rank 0 to the others; the data path is
 the library's own RCCL communicator.
 
+Every native round runs on fp32 buckets: on a native 16-bit layout
+(``BucketLayout(native16=True)``) the aggregators below raise ValueError
+before touching the library (they used to hand 16-bit buckets to fp32
+kernels).  The 16-bit striped round runs over torch.distributed
+(``dist.StripedAggregator``); ``describe`` and ``round_model``
+give its schedule and modelled cost.
+
 No fallback: loading raises if libfedagg_comm.so is missing.
 """
 from __future__ import annotations
@@ -28,6 +35,7 @@ import torch
 from . import _lib
 from .dist import check_final, shard_counts
 from .layout import BucketLayout
+from .partition import layout_elem
 
 COMM_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfedagg_comm.so")
 FA_E_COMM = -6
@@ -43,7 +51,8 @@ COMM_EXPORTS = ["fa_comm_unique_id", "fa_comm_init_rank", "fa_comm_init", "fa_co
                 "fa_multi_plan_mode", "fa_multi_plan_destroy", "fa_reduce_multi",
                 "fa_mean_f32_multi_ex", "fa_stripe_plan_create_ex", "fa_multi_select_layout",
                 "fa_multi_plan_chunks", "fa_round_model", "fa_comm_set_profile",
-                "fa_round_plan_profile", "fa_model_constants"]
+                "fa_round_plan_profile", "fa_model_constants", "fa_describe_round_elem",
+                "fa_round_model_elem"]
 
 FA_XCHG_REDUCE, FA_XCHG_RS_GATHER = 0, 1
 FA_MODE_SHARDED, FA_MODE_STRIPED, FA_MODE_CHAINED, FA_MODE_BLOCKED = 0, 1, 2, 3
@@ -148,6 +157,9 @@ def _load():
         "fa_round_plan_profile": [_P, ctypes.POINTER(FaRoundProfile)],
         "fa_model_constants": [ctypes.POINTER(ctypes.c_double)] * 4,
     }
+    # the element-aware host entries: the fp32 signature plus the element type
+    sig["fa_describe_round_elem"] = sig["fa_describe_round"] + [_I]
+    sig["fa_round_model_elem"] = sig["fa_round_model"] + [_I]
     for name, args in sig.items():
         fn = getattr(lib, name)
         fn.restype = _I
@@ -208,10 +220,14 @@ def round_model(mode: int, layout: BucketLayout, counts: Sequence[int], nchunks:
     modelled time in microseconds, the largest byte count on one link
     direction, the largest per-rank HBM byte count, group and step counts."""
     out = FaRoundCost()
-    _lib.check(lib().fa_round_model(int(mode), len(counts), _counts(counts),
-                                    *_layout_args(layout), int(nchunks), int(exchange),
-                                    _lib.FA_PLAN_GAPS_ARE_PADDING, int(root), int(bool(weighted)),
-                                    ctypes.byref(out)), "fa_round_model")
+    args = (int(mode), len(counts), _counts(counts), *_layout_args(layout), int(nchunks),
+            int(exchange), _lib.FA_PLAN_GAPS_ARE_PADDING, int(root), int(bool(weighted)),
+            ctypes.byref(out))
+    elem = layout_elem(layout)
+    if elem is None:
+        _lib.check(lib().fa_round_model(*args), "fa_round_model")
+    else:   # a native 16-bit layout: 2 bytes per element on the links and in HBM
+        _lib.check(lib().fa_round_model_elem(*args, elem), "fa_round_model_elem")
     return {f: getattr(out, f) for f, _ in FaRoundCost._fields_}
 
 
@@ -239,13 +255,19 @@ def describe(mode: int, layout: BucketLayout, counts: Sequence[int], rank: int,
              weighted: bool = False) -> List[dict]:
     """Rank ``rank``'s schedule of one round (fa_describe_round): the exact
     list of exchanges and kernels the native executor issues, computed on the
-    host (no GPU, no communicator)."""
+    host (no GPU, no communicator).  A native 16-bit layout: the 16-bit
+    round's (fa_describe_round_elem; offsets and counts in 16-bit elements)."""
     n = _I()
     args = (mode, len(counts), rank, _counts(counts), *_layout_args(layout), int(nchunks),
             int(exchange), _lib.FA_PLAN_GAPS_ARE_PADDING, int(root), int(bool(weighted)))
-    _lib.check(lib().fa_describe_round(*args, None, 0, ctypes.byref(n)), "fa_describe_round")
+    elem = layout_elem(layout)
+    if elem is None:
+        fn, tail, name = lib().fa_describe_round, (), "fa_describe_round"
+    else:
+        fn, tail, name = lib().fa_describe_round_elem, (elem,), "fa_describe_round_elem"
+    _lib.check(fn(*args, None, 0, ctypes.byref(n), *tail), name)
     arr = (FaXfer * max(1, n.value))()
-    _lib.check(lib().fa_describe_round(*args, arr, n.value, ctypes.byref(n)), "fa_describe_round")
+    _lib.check(fn(*args, arr, n.value, ctypes.byref(n), *tail), name)
     out = []
     for i in range(n.value):
         x = arr[i]
@@ -449,6 +471,11 @@ class NativeShardedAggregator:
         size (NativeAggregator alone asks; the other forms take any counts
         that name this rank's shard and sum to ``n_total``)."""
         check_final(final)
+        if layout_elem(layout) is not None:
+            # before the plan: every rank refuses alike, nobody waits in an exchange
+            raise ValueError(f"{type(self).__name__}: the native rounds run on fp32 buckets; a "
+                             f"native {layout.float_dtype} layout takes dist.StripedAggregator "
+                             "(the striped round over torch.distributed)")
         world, rank, _ = comm.info()
         if counts is None:
             counts = shard_counts(n_total, world)

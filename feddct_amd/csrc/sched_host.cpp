@@ -2,7 +2,7 @@
 // (sched_host.h): the geometry, the five schedule builders, the stream rules,
 // the discrete-event model and the host-only entry points of fedagg_comm.h.
 // Plain C++17: no HIP header, no RCCL header, no device.  Of libfedagg.so it
-// calls fa_plan_build_host and fa_chain_levels (plan_host.cpp, as HIP-free).
+// calls fa_plan_build_host_elem and fa_chain_levels (plan_host.cpp, as HIP-free).
 
 #include "sched_host.h"
 
@@ -30,7 +30,9 @@ int check_round_args(const char* who, int mode, int* nchunks, int xchg, int root
 // ------------------------------------------------------------- geometry ----
 int make_geo(int nranks, int rank, const int* counts, const fa_seg* seg32, int nseg32,
              int64_t f32_numel, const fa_seg* seg64, int nseg64, int64_t i64_numel,
-             unsigned flags, const char* who, Geo* g) {
+             unsigned flags, const char* who, Geo* g, int elem) {
+  if (elem != FA_ELEM_F32 && elem != FA_ELEM_F16 && elem != FA_ELEM_BF16)
+    return set_err(FA_E_INVAL, "%s: elem=%d", who, elem);
   if (!counts) return set_err(FA_E_INVAL, "%s: counts is NULL", who);
   if (nranks < 1 || rank < 0 || rank >= nranks)
     return set_err(FA_E_INVAL, "%s: rank %d of %d", who, rank, nranks);
@@ -58,13 +60,15 @@ int make_geo(int nranks, int rank, const int* counts, const fa_seg* seg32, int n
   g->f32_numel = f32_numel;
   g->i64_numel = i64_numel;
   g->flags = flags;
+  g->elem = elem;
+  // (FA_ELEM_F32: fa_plan_build_host's table)
   fa_plan_info info{};
-  int rc = fa_plan_build_host(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags,
-                              nullptr, 0, &info);
+  int rc = fa_plan_build_host_elem(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags,
+                                   elem, nullptr, 0, &info);
   if (rc) return rc;
   std::vector<fa_tile_desc> tiles(std::max(1, info.ntiles));
-  rc = fa_plan_build_host(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags,
-                          tiles.data(), info.ntiles, &info);
+  rc = fa_plan_build_host_elem(seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, 0, flags,
+                               elem, tiles.data(), info.ntiles, &info);
   if (rc) return rc;
   tiles.resize(info.ntiles);
   g->t32.clear();
@@ -75,19 +79,38 @@ int make_geo(int nranks, int rank, const int* counts, const fa_seg* seg32, int n
   return FA_OK;
 }
 
+int check_round_elem(const char* who, int elem, int mode, int weighted) {
+  if (elem == FA_ELEM_F32) return FA_OK;
+  if (elem != FA_ELEM_F16 && elem != FA_ELEM_BF16)
+    return set_err(FA_E_INVAL, "%s: elem=%d", who, elem);
+  if (mode != FA_MODE_STRIPED)
+    return set_err(FA_E_INVAL,
+                   "%s: mode %d on a 16-bit bucket: only the striped round (FA_MODE_STRIPED) "
+                   "runs on fp16 / bf16 buckets (the other forms move fp32 sums or cascade state)",
+                   who, mode);
+  if (weighted)
+    return set_err(FA_E_INVAL,
+                   "%s: a weighted round on a 16-bit bucket: the pre-multiplied rows are fp32 "
+                   "values, which a 16-bit exchange cannot carry",
+                   who);
+  return FA_OK;
+}
+
 namespace {
 
 // k contiguous groups of sorted tiles with equal shares of the elements, cut
-// only before a vector tile on a 256-B boundary; exactly k groups, trailing
-// ones may be empty.  Group g = tiles [cut[g], cut[g+1]).
-void cut_tiles(const std::vector<fa_tile_desc>& t, int k, std::vector<size_t>* cut) {
+// only before a vector tile on a 256-B boundary (`align` elements: 64 fp32,
+// 128 fp16 / bf16); exactly k groups, trailing ones may be empty.  Group g =
+// tiles [cut[g], cut[g+1]).
+void cut_tiles(const std::vector<fa_tile_desc>& t, int k, std::vector<size_t>* cut,
+               int align = 64) {
   int64_t total = 0;
   for (const fa_tile_desc& x : t) total += x.count;
   cut->assign(1, 0);
   int64_t acc = 0;
   for (size_t i = 0; i < t.size(); ++i) {
     const int c = (int)cut->size();
-    if (c < k && i > 0 && acc >= total * c / k && t[i].kind == 0 && t[i].start % 64 == 0)
+    if (c < k && i > 0 && acc >= total * c / k && t[i].kind == 0 && t[i].start % align == 0)
       cut->push_back(i);
     acc += t[i].count;
   }
@@ -590,7 +613,7 @@ int build_round(RoundGeo* p, int nchunks, std::vector<fa_tile_desc>* vec_out,
   } else if (p->mode == FA_MODE_STRIPED) {
     // stripes, then each stripe's tiles cut into nchunks column chunks
     std::vector<size_t> cut;
-    cut_tiles(g.t32, g.nranks, &cut);
+    cut_tiles(g.t32, g.nranks, &cut, cut_align(g.elem));
     p->lo = cut_bounds(g.t32, cut, g.f32_numel);
     p->nchunks = nchunks;
     p->clo.assign(g.nranks, std::vector<int64_t>());
@@ -598,7 +621,7 @@ int build_round(RoundGeo* p, int nchunks, std::vector<fa_tile_desc>* vec_out,
     for (int r = 0; r < g.nranks; ++r) {
       const std::vector<fa_tile_desc> sub(g.t32.begin() + cut[r], g.t32.begin() + cut[r + 1]);
       std::vector<size_t> sc;
-      cut_tiles(sub, nchunks, &sc);
+      cut_tiles(sub, nchunks, &sc, cut_align(g.elem));
       std::vector<int64_t>& b = p->clo[r];
       b.assign(nchunks + 1, p->lo[r + 1]);
       b[0] = p->lo[r];
@@ -704,8 +727,8 @@ int popc(unsigned v) { return __builtin_popcount(v); }
 // HBM bytes a kernel op reads and writes (the columns it covers; count 0 =
 // the vector columns, V elements); the scalar-column stacks and their
 // reductions are a few KB and cost only their launch.
-double kernel_bytes(const fa_xfer& x, int n_total, int64_t V) {
-  const double b = 4.0 * (double)(x.count > 0 ? x.count : V);
+double kernel_bytes(const fa_xfer& x, int n_total, int64_t V, int es) {
+  const double b = (double)es * (double)(x.count > 0 ? x.count : V);
   switch (x.op) {
     case FA_X_K_SUM:
     case FA_X_K_STRIPE:
@@ -726,15 +749,16 @@ double kernel_bytes(const fa_xfer& x, int n_total, int64_t V) {
   }
 }
 
-double elem_bytes(const fa_xfer& x) {
+// (es: bytes per element of the floating bucket, 2 in a 16-bit round)
+double elem_bytes(const fa_xfer& x, int es) {
   const int buf = x.op == FA_X_RECV ? x.dst : x.src;
   const int idx = x.op == FA_X_RECV ? x.dst_index : x.src_index;
-  return is_i64(buf, idx) ? 8.0 : 4.0;
+  return is_i64(buf, idx) ? 8.0 : (double)es;
 }
 
 // A collective's bytes on each link direction of a rank (ring algorithms).
-double coll_link_bytes(const fa_xfer& x, int W) {
-  const double es = elem_bytes(x), n = (double)x.count * es;
+double coll_link_bytes(const fa_xfer& x, int W, int esz) {
+  const double es = elem_bytes(x, esz), n = (double)x.count * es;
   switch (x.op) {
     case FA_X_ALLGATHER:
       return x.src == FA_B_PARTIAL ? n * (W - 1) / W : n * (W - 1);
@@ -745,7 +769,7 @@ double coll_link_bytes(const fa_xfer& x, int W) {
 }
 
 int model_schedules(const std::vector<std::vector<fa_xfer>>& sch, int n_total, int64_t V,
-                    fa_round_cost* out) {
+                    fa_round_cost* out, int es = 4) {
   const int W = (int)sch.size();
   std::vector<size_t> pos(W, 0);
   std::vector<char> posted(W, 0);
@@ -839,12 +863,12 @@ int model_schedules(const std::vector<std::vector<fa_xfer>>& sch, int n_total, i
         if (!is_comm(x.op)) continue;
         comm = true;
         if (x.op == FA_X_SEND || x.op == FA_X_RECV) {
-          const double b = (double)x.count * elem_bytes(x);
+          const double b = (double)x.count * elem_bytes(x, es);
           (x.op == FA_X_SEND ? go : gi)[x.peer] += b;
           (x.op == FA_X_SEND ? lout : lin)[r][x.peer] += b;
           ghbm += b;
         } else {
-          const double b = coll_link_bytes(x, W);
+          const double b = coll_link_bytes(x, W, es);
           gcoll += b;
           ghbm += 2.0 * b;
         }
@@ -859,7 +883,7 @@ int model_schedules(const std::vector<std::vector<fa_xfer>>& sch, int n_total, i
       for (size_t i = pos[r]; i < e; ++i) {
         const fa_xfer& x = o[i];
         if (is_comm(x.op)) continue;
-        const double kb = kernel_bytes(x, n_total, V);
+        const double kb = kernel_bytes(x, n_total, V, es);
         const double dur = mc().kernel_us + us_hbm(kb);
         hbm[r] += kb;
         if (on_comm_stream(x)) {
@@ -895,7 +919,8 @@ int model_schedules(const std::vector<std::vector<fa_xfer>>& sch, int n_total, i
 fa_round_cost one_rank_cost(const Geo& g) {
   fa_round_cost c{};
   c.hbm_bytes_max =
-      (double)(g.n_total + 1) * (4.0 * (double)g.f32_numel + 8.0 * (double)g.i64_numel);
+      (double)(g.n_total + 1) *
+      ((double)elem_size(g.elem) * (double)g.f32_numel + 8.0 * (double)g.i64_numel);
   c.model_us = mc().kernel_us + us_hbm(c.hbm_bytes_max);
   c.steps = 1;
   return c;
@@ -981,22 +1006,24 @@ int select_form(const Geo& base, unsigned mflags, int* mode, int* nchunks, doubl
 // ====================================================== host-only view =====
 using namespace fa_sched;
 
-extern "C" {
+namespace {
 
-int fa_describe_round(int mode, int nranks, int rank, const int* counts, const fa_seg* seg32,
-                      int nseg32, int64_t f32_numel, const fa_seg* seg64, int nseg64,
-                      int64_t i64_numel, int nchunks, int exchange, unsigned flags, int root,
-                      int weighted, fa_xfer* ops, int cap, int* nops) {
-  if (!nops) return set_err(FA_E_INVAL, "fa_describe_round: nops is NULL");
+// fa_describe_round[_elem]; `who`: the entry called, for the messages.
+int describe_round(const char* who, int mode, int nranks, int rank, const int* counts,
+                   const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
+                   int nseg64, int64_t i64_numel, int nchunks, int exchange, unsigned flags,
+                   int root, int weighted, fa_xfer* ops, int cap, int* nops, int elem) {
+  if (!nops) return set_err(FA_E_INVAL, "%s: nops is NULL", who);
   *nops = 0;
-  int rc = check_round_args("fa_describe_round", mode, &nchunks, exchange, root, nranks);
+  int rc = check_round_args(who, mode, &nchunks, exchange, root, nranks);
   if (rc) return rc;
+  if ((rc = check_round_elem(who, elem, mode, weighted))) return rc;
   RoundGeo p;
   p.mode = mode;
   p.xchg = exchange;
   p.req_chunks = nchunks;
   rc = make_geo(nranks, rank, counts, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, flags,
-                "fa_describe_round", &p.g);
+                who, &p.g, elem);
   if (rc) return rc;
   std::vector<fa_tile_desc> vec, tails;
   std::vector<size_t> cut;
@@ -1006,10 +1033,57 @@ int fa_describe_round(int mode, int nranks, int rank, const int* counts, const f
   *nops = (int)s.size();
   if (ops) {
     if (cap < (int)s.size())
-      return set_err(FA_E_RANGE, "fa_describe_round: %d ops, capacity %d", (int)s.size(), cap);
+      return set_err(FA_E_RANGE, "%s: %d ops, capacity %d", who, (int)s.size(), cap);
     std::copy(s.begin(), s.end(), ops);
   }
   return FA_OK;
+}
+
+// fa_round_model[_elem]
+int round_model(const char* who, int mode, int nranks, const int* counts, const fa_seg* seg32,
+                int nseg32, int64_t f32_numel, const fa_seg* seg64, int nseg64,
+                int64_t i64_numel, int nchunks, int exchange, unsigned flags, int root,
+                int weighted, fa_round_cost* out, int elem) {
+  if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
+  int rc = check_round_args(who, mode, &nchunks, exchange, root, nranks);
+  if (rc) return rc;
+  if ((rc = check_round_elem(who, elem, mode, weighted))) return rc;
+  Geo g;
+  rc = make_geo(nranks, 0, counts, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, flags, who,
+                &g, elem);
+  if (rc) return rc;
+  if (nranks == 1) {
+    *out = one_rank_cost(g);
+    return FA_OK;
+  }
+  std::vector<std::vector<fa_xfer>> sch;
+  int64_t V = 0;
+  if ((rc = all_schedules(g, mode, nchunks, exchange, root, weighted != 0, &sch, &V))) return rc;
+  return model_schedules(sch, g.n_total, V, out, elem_size(g.elem));
+}
+
+}  // namespace
+
+extern "C" {
+
+int fa_describe_round(int mode, int nranks, int rank, const int* counts, const fa_seg* seg32,
+                      int nseg32, int64_t f32_numel, const fa_seg* seg64, int nseg64,
+                      int64_t i64_numel, int nchunks, int exchange, unsigned flags, int root,
+                      int weighted, fa_xfer* ops, int cap, int* nops) {
+  return describe_round("fa_describe_round", mode, nranks, rank, counts, seg32, nseg32, f32_numel,
+                        seg64, nseg64, i64_numel, nchunks, exchange, flags, root, weighted, ops,
+                        cap, nops, FA_ELEM_F32);
+}
+
+// (FA_ELEM_F32 is the fp32 entry exactly, its name in the messages included)
+int fa_describe_round_elem(int mode, int nranks, int rank, const int* counts,
+                           const fa_seg* seg32, int nseg32, int64_t f32_numel,
+                           const fa_seg* seg64, int nseg64, int64_t i64_numel, int nchunks,
+                           int exchange, unsigned flags, int root, int weighted, fa_xfer* ops,
+                           int cap, int* nops, int elem) {
+  return describe_round(elem == FA_ELEM_F32 ? "fa_describe_round" : "fa_describe_round_elem",
+                        mode, nranks, rank, counts, seg32, nseg32, f32_numel, seg64, nseg64,
+                        i64_numel, nchunks, exchange, flags, root, weighted, ops, cap, nops, elem);
 }
 
 int fa_model_constants(double* link_gbps, double* hbm_gbps, double* group_us,
@@ -1026,21 +1100,17 @@ int fa_round_model(int mode, int nranks, const int* counts, const fa_seg* seg32,
                    int64_t f32_numel, const fa_seg* seg64, int nseg64, int64_t i64_numel,
                    int nchunks, int exchange, unsigned flags, int root, int weighted,
                    fa_round_cost* out) {
-  if (!out) return set_err(FA_E_INVAL, "fa_round_model: out is NULL");
-  int rc = check_round_args("fa_round_model", mode, &nchunks, exchange, root, nranks);
-  if (rc) return rc;
-  Geo g;
-  rc = make_geo(nranks, 0, counts, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, flags,
-                "fa_round_model", &g);
-  if (rc) return rc;
-  if (nranks == 1) {
-    *out = one_rank_cost(g);
-    return FA_OK;
-  }
-  std::vector<std::vector<fa_xfer>> sch;
-  int64_t V = 0;
-  if ((rc = all_schedules(g, mode, nchunks, exchange, root, weighted != 0, &sch, &V))) return rc;
-  return model_schedules(sch, g.n_total, V, out);
+  return round_model("fa_round_model", mode, nranks, counts, seg32, nseg32, f32_numel, seg64,
+                     nseg64, i64_numel, nchunks, exchange, flags, root, weighted, out, FA_ELEM_F32);
+}
+
+int fa_round_model_elem(int mode, int nranks, const int* counts, const fa_seg* seg32, int nseg32,
+                        int64_t f32_numel, const fa_seg* seg64, int nseg64, int64_t i64_numel,
+                        int nchunks, int exchange, unsigned flags, int root, int weighted,
+                        fa_round_cost* out, int elem) {
+  return round_model(elem == FA_ELEM_F32 ? "fa_round_model" : "fa_round_model_elem", mode, nranks,
+                     counts, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, nchunks, exchange,
+                     flags, root, weighted, out, elem);
 }
 
 // The default multi-GPU entry's choice (fedcomm.hip fa_multi_plan_create):

@@ -6,8 +6,8 @@
 // compiled as plain C++ and runs without a device or a communicator).
 // fedcomm.hip owns the kernels, the plans' device resources, the executor,
 // graph capture and the RCCL-facing C ABI; the host-only entry points
-// (fa_describe_round, fa_round_model, fa_model_constants, fa_multi_select*)
-// are defined in sched_host.cpp.
+// (fa_describe_round[_elem], fa_round_model[_elem], fa_model_constants,
+// fa_multi_select*) are defined in sched_host.cpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -27,8 +27,16 @@ struct Geo {
   int n_total = 0, n_local = 0, lo_slot = 0, nmax = 0;
   int64_t f32_numel = 0, i64_numel = 0;
   unsigned flags = 0;
-  std::vector<fa_tile_desc> t32, t64;  // fp32 tiles sorted by start; int64 tiles
+  int elem = FA_ELEM_F32;  // the floating bucket's element type (FA_ELEM_*)
+  // floating tiles sorted by start (fp32, or 16-bit: in 16-bit elements, vector
+  // tiles on 8-element boundaries); int64 tiles
+  std::vector<fa_tile_desc> t32, t64;
 };
+
+// Bytes per element of the floating bucket; elements per 256 B of it, where
+// cut_tiles may cut (64 fp32, 128 fp16 / bf16: partition.cut_align).
+inline int elem_size(int elem) { return elem == FA_ELEM_F32 ? 4 : 2; }
+inline int cut_align(int elem) { return 256 / elem_size(elem); }
 
 // Chained: state hops rank to rank, chunk by chunk.
 struct ChainGeo {
@@ -81,9 +89,15 @@ constexpr int kStripeChunks = 4;
 // else 8; then 1..FA_COMM_MAX_CHUNKS), the exchange kind, root < nranks.
 int check_round_args(const char* who, int mode, int* nchunks, int xchg, int root, int nranks);
 
+// elem: FA_ELEM_F16 / FA_ELEM_BF16 builds the 16-bit table
+// (fa_plan_build_host_elem), in 16-bit elements; another value is FA_E_INVAL.
 int make_geo(int nranks, int rank, const int* counts, const fa_seg* seg32, int nseg32,
              int64_t f32_numel, const fa_seg* seg64, int nseg64, int64_t i64_numel,
-             unsigned flags, const char* who, Geo* g);
+             unsigned flags, const char* who, Geo* g, int elem = FA_ELEM_F32);
+
+// What a 16-bit round supports: the striped form, unweighted (`who` names the
+// entry in the message).  FA_ELEM_F32 passes everything.
+int check_round_elem(const char* who, int elem, int mode, int weighted);
 
 // The cut of r->g for r->mode.  The tile lists are what a plan's device side
 // is created from: chunk c = tiles [cut[c], cut[c + 1]) of g.t32 (e1, e2) or

@@ -30,6 +30,10 @@ round exists natively only).  The round forms:
   clients) max 22,938 ULP, histogram in comm.E1_ULP_R04; bench.py's N>1
   line reports it beside the time.
 
+On a native 16-bit layout (``BucketLayout(native16=True)``) the striped round
+is the only form: it runs on the fp16 / bf16 buckets themselves, unweighted
+(DESIGN §4.14); ``Aggregator`` takes it, the other two classes refuse.
+
 int64 keys (a few bytes) always travel raw — an all-gather of every rank's
 int64 buckets — and are reduced exactly over all N_total clients.
 
@@ -99,7 +103,11 @@ def exact_form(counts: Sequence[int], layout: Optional[BucketLayout] = None,
     form with the lowest modelled time (sched_host.cpp fa_multi_select_layout
     on ``layout``; None: fa_multi_select's nominal layout) — "blocked" (only
     where ``blocked_allowed``), "chained" or "striped".  ``root_all``: the
-    result goes to every rank.  r05: "blocked" if allowed, else "chained"."""
+    result goes to every rank.  r05: "blocked" if allowed, else "chained".
+    A native 16-bit layout: always "striped" (the other forms move fp32 sums
+    or cascade state)."""
+    if layout is not None and layout.native16:
+        return "striped"   # the one exact form on fp16 / bf16 buckets
     from .comm import multi_select
     return multi_select(counts, layout=layout, root_all=root_all)
 
@@ -162,6 +170,14 @@ def p2p(ops, group=None):
         req.wait()
     for t, h in back:
         t.copy_(h)
+
+
+def refuse_native16(layout: BucketLayout, who: str) -> None:
+    """The rounds that exist on fp32 buckets only."""
+    if layout.native16:
+        raise ValueError(f"{who}: a native {layout.float_dtype} layout runs the striped round "
+                         "only (StripedAggregator / Aggregator): this form moves fp32 sums or "
+                         "cascade state")
 
 
 def chunk_segments(layout: BucketLayout, nchunks: int):
@@ -250,6 +266,7 @@ class ShardedAggregator:
         check_final(final)
         if exchange not in ("reduce", "rs_gather"):
             raise ValueError(f"exchange must be 'reduce' or 'rs_gather', not {exchange!r}")
+        refuse_native16(layout, "ShardedAggregator")
         self.exchange = exchange
         self.final = final
         self.root = root
@@ -354,14 +371,26 @@ class ShardedAggregator:
 # --------------------------------------------------------------------------
 class HipStripeBackend(_HipI64):
     """Stripe-chunk reductions with the HIP kernel over tile-subset plans
-    (one per chunk of this rank's stripe)."""
+    (one per chunk of this rank's stripe).  ``elem``: the floating bucket's
+    element type (default: the layout's — FA_ELEM_F16 / FA_ELEM_BF16 on a
+    native 16-bit layout, whose chunk plans are 16-bit ones)."""
 
-    def __init__(self, layout: BucketLayout, chunk_tiles, tiles64):
+    def __init__(self, layout: BucketLayout, chunk_tiles, tiles64, elem=None):
         from . import _lib
+        from .partition import layout_elem
         self._lib = _lib
         te = 0
-        self.plans = [_lib.Plan(None, layout.f32_numel, None, layout.i64_numel, te, tiles=t)
-                      if len(t) else None for t in chunk_tiles]
+        if elem is None:
+            elem = layout_elem(layout)
+        self.elem = _lib.FA_ELEM_F32 if elem is None else int(elem)
+        self.esize = 4 if self.elem == _lib.FA_ELEM_F32 else 2
+        if self.elem == _lib.FA_ELEM_F32:
+            self.plans = [_lib.Plan(None, layout.f32_numel, None, layout.i64_numel, te, tiles=t)
+                          if len(t) else None for t in chunk_tiles]
+        else:
+            self.plans = [_lib.Plan.from_tiles(t, layout.f32_numel, layout.i64_numel, te,
+                                               _lib.FA_PLAN_GAPS_ARE_PADDING, self.elem)
+                          if len(t) else None for t in chunk_tiles]
         self.plan64 = (_lib.Plan(None, layout.f32_numel, None, layout.i64_numel, te,
                                  tiles=tiles64) if len(tiles64) else None)
 
@@ -372,7 +401,9 @@ class HipStripeBackend(_HipI64):
         if self.plans[c] is None:
             return
         L = self._lib
-        ptrs = [t.data_ptr() - 4 * base for t, base in sources]
+        if weights is not None and self.esize != 4:
+            raise ValueError("HipStripeBackend: weighted rounds on 16-bit buckets are not built")
+        ptrs = [t.data_ptr() - self.esize * base for t, base in sources]
         w = None if weights is None else (ctypes.c_float * len(weights))(*map(float, weights))
         L.check(L.lib.fa_reduce(self.plans[c].handle, L.ptr_array(ptrs), None, len(ptrs), w,
                                 out32.data_ptr(), None, 0, self._stream()),
@@ -406,8 +437,11 @@ class StripedAggregator:
     def __init__(self, layout: BucketLayout, n_total: int, out32: torch.Tensor,
                  out64: torch.Tensor, group=None, backend=None, final: str = "allreduce",
                  root: int = 0, nchunks: int = 4, counts: Optional[Sequence[int]] = None):
-        from .partition import i64_tiles, layout_tiles, stripe_chunks
+        from .partition import cut_align, i64_tiles, layout_tiles, stripe_chunks
         check_final(final)
+        if layout.native16 and out32.dtype != layout.float_dtype:
+            raise TypeError(f"StripedAggregator: a {out32.dtype} result bucket on a "
+                            f"{layout.float_dtype} layout")
         self.final = final
         self.root = root if final == "reduce" else -1
         self.layout = layout
@@ -425,16 +459,19 @@ class StripedAggregator:
         first = [sum(self.counts[:r]) for r in range(self.world)]
         self.shards = [(first[r], first[r] + self.counts[r]) for r in range(self.world)]
         info, tiles = layout_tiles(layout)
-        self.chunks = stripe_chunks(tiles, self.world, layout.f32_numel, nchunks)
+        self.chunks = stripe_chunks(tiles, self.world, layout.f32_numel, nchunks,
+                                    cut_align(layout))
         self.bounds = [[c[0] for c in ch] + [ch[-1][1]] for ch in self.chunks]
         self.ranges = [(b[0], b[-1]) for b in self.bounds]
         self.lo, self.hi = self.ranges[self.rank]
         self.backend = backend or HipStripeBackend(layout, [t for _, _, t in self.chunks[self.rank]],
                                                    i64_tiles(tiles))
         L = self.hi - self.lo
-        self.lpad = (L + 3) // 4 * 4
+        # rows stay 16-B aligned: 4 floats, 8 elements of a 16-bit layout
+        q = 8 if layout.native16 else 4
+        self.lpad = (L + q - 1) // q * q
         dev = out32.device
-        self.recv = torch.zeros((n_total, max(self.lpad, 4)), dtype=torch.float32, device=dev)
+        self.recv = torch.zeros((n_total, max(self.lpad, q)), dtype=layout.float_dtype, device=dev)
         self.stage = None   # weighted rounds: pre-multiplied local clients
         nmax = max(1, max(self.counts))
         width = max(1, layout.i64_numel)
@@ -468,6 +505,7 @@ class StripedAggregator:
         a, b = self.shards[me]
         if len(local32) != b - a:
             raise ValueError(f"rank {me} holds {len(local32)} clients, shard is {b - a}")
+        self._check16(local32, weights)
         self._i64(local64)
         send = local32
         wfull = None
@@ -508,10 +546,25 @@ class StripedAggregator:
                 _, c, off, cnt = red
                 self.backend.reduce_chunk(c, off, off + cnt, sources, dst, wfull)
 
+    def _check16(self, tensors, weights=None):
+        """A native 16-bit layout's round: buckets of the layout's dtype, no
+        weights — checked before any exchange, so every rank refuses alike."""
+        if not self.layout.native16:
+            return
+        if weights is not None:
+            raise ValueError("StripedAggregator: weighted rounds on 16-bit buckets are not built "
+                             "(the pre-multiplied rows are fp32 values)")
+        for t in tensors:
+            if t.dtype != self.layout.float_dtype:
+                raise TypeError(f"StripedAggregator: a {t.dtype} bucket on a native "
+                                f"{self.layout.float_dtype} layout")
+
     def step_host(self, stripes32: Sequence[torch.Tensor], clients64: Sequence[torch.Tensor],
                   local64: Optional[List[torch.Tensor]] = None) -> None:
         """``stripes32[k]``: client slot k's values for THIS rank's columns
-        [lo, hi) (host, pinned), ``clients64[k]``: its int64 bucket."""
+        [lo, hi) (host, pinned; the layout's dtype), ``clients64[k]``: its
+        int64 bucket."""
+        self._check16(stripes32)
         L = self.hi - self.lo
         for k, t in enumerate(stripes32):
             self.recv[k, :L].copy_(t, non_blocking=True)
@@ -615,6 +668,7 @@ class ChainAggregator:
                  root: int = 0, nchunks: int = 16, counts: Optional[Sequence[int]] = None):
         from .partition import chain_cut
         check_final(final)
+        refuse_native16(layout, "ChainAggregator")
         self.layout, self.n_total = layout, n_total
         self.out32, self.out64 = out32, out64
         self.group = group
@@ -779,8 +833,18 @@ class Aggregator:
             self.form = "e1/torch.distributed"
             self._step = self._agg.step
             return
+        if layout.native16 and exact and weights is not None:
+            raise ValueError("Aggregator: weighted rounds on 16-bit buckets are not built (the "
+                             "pre-multiplied rows are fp32 values)")
+        if layout.native16 and backend is not None and stripe_backend is None:
+            # (the fp32 path keeps its behaviour: there the model may still pick
+            # the chained form, which ``backend`` serves)
+            raise ValueError("Aggregator: a native 16-bit layout runs the striped round, whose "
+                             "arithmetic backend is `stripe_backend`; `backend` (the chained "
+                             "form's) alone would silently mix in HipStripeBackend")
         if native is None:
-            native = (backend is None and stripe_backend is None
+            # (the native rounds run on fp32 buckets only)
+            native = (backend is None and stripe_backend is None and not layout.native16
                       and "nccl" in str(dist.get_backend(group)))
         if native:
             from .comm import Comm, NativeAggregator

@@ -93,14 +93,15 @@ def split_tiles(tiles: np.ndarray, parts: int, f32_numel: int, fractions=None, a
     return out
 
 
-def stripe_chunks(tiles: np.ndarray, parts: int, f32_numel: int, nchunks: int):
+def stripe_chunks(tiles: np.ndarray, parts: int, f32_numel: int, nchunks: int, align: int = 64):
     """The striped round's cut (sched_host.cpp build_round, r06): ``parts``
     stripes (split_tiles), each cut into ``nchunks`` column chunks by the
-    same rule.  Returns, per stripe, [(lo, hi, tiles)] of its chunks, in
-    order, covering the stripe exactly (trailing chunks may be empty)."""
+    same rule, at multiples of ``align`` elements (``cut_align``).  Returns,
+    per stripe, [(lo, hi, tiles)] of its chunks, in order, covering the
+    stripe exactly (trailing chunks may be empty)."""
     out = []
-    for lo, hi, sub in split_tiles(tiles, parts, f32_numel):
-        ci = cut_index(sub, nchunks)
+    for lo, hi, sub in split_tiles(tiles, parts, f32_numel, align=align):
+        ci = cut_index(sub, nchunks, align=align)
         b = [lo] + [int(sub[ci[c], 0]) if ci[c] < len(sub) else hi
                     for c in range(1, nchunks)] + [hi]
         out.append([(b[c], b[c + 1], sub[ci[c]:ci[c + 1]]) for c in range(nchunks)])

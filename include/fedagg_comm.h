@@ -381,6 +381,20 @@ int fa_describe_round(int mode, int nranks, int rank, const int *counts,
                       const fa_seg *seg64, int nseg64, int64_t i64_numel,
                       int nchunks, int exchange, unsigned flags, int root,
                       int weighted, fa_xfer *ops, int cap, int *nops);
+/* ... over a floating bucket of `elem` elements (FA_ELEM_*; FA_ELEM_F32:
+ * fa_describe_round exactly).  FA_ELEM_F16 / FA_ELEM_BF16: the layout, the
+ * offsets and the counts are in 16-bit elements, cuts fall on 128-element
+ * (256-B) boundaries; a mode other than FA_MODE_STRIPED, or weighted != 0, is
+ * FA_E_INVAL (the message names the reason).  Host only, as fa_round_model_elem:
+ * every plan-creating entry of this library makes fp32 plans; the executor of
+ * the 16-bit striped round is not part of it yet (feddct_amd/dist.py runs the
+ * round over torch.distributed). */
+int fa_describe_round_elem(int mode, int nranks, int rank, const int *counts,
+                           const fa_seg *seg32, int nseg32, int64_t f32_numel,
+                           const fa_seg *seg64, int nseg64, int64_t i64_numel,
+                           int nchunks, int exchange, unsigned flags, int root,
+                           int weighted, fa_xfer *ops, int cap, int *nops,
+                           int elem);
 
 /* ---- the round cost model (r06), host only ---------------------------------
  * Every rank's schedule (fa_describe_round) timed by a discrete-event replay
@@ -433,6 +447,15 @@ int fa_round_model(int mode, int nranks, const int *counts, const fa_seg *seg32,
                    int nseg32, int64_t f32_numel, const fa_seg *seg64, int nseg64,
                    int64_t i64_numel, int nchunks, int exchange, unsigned flags,
                    int root, int weighted, fa_round_cost *out);
+/* ... of a round over a floating bucket of `elem` elements (FA_ELEM_F32:
+ * fa_round_model exactly).  A 16-bit round counts 2 bytes per element of
+ * CLIENT / RECV / OUT / STRIPE traffic, on the links and in HBM (int64 keys
+ * stay 8); refusals as fa_describe_round_elem. */
+int fa_round_model_elem(int mode, int nranks, const int *counts,
+                        const fa_seg *seg32, int nseg32, int64_t f32_numel,
+                        const fa_seg *seg64, int nseg64, int64_t i64_numel,
+                        int nchunks, int exchange, unsigned flags, int root,
+                        int weighted, fa_round_cost *out, int elem);
 
 #ifdef __cplusplus
 }
