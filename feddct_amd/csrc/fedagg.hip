@@ -1605,6 +1605,9 @@ struct ClientTable {
       e = table_fill(ctable, host, st);
     } else {
       e = table_alloc(&owned, host.size(), st);
+      // `host` dies at return: this relies on the runtime staging a pageable
+      // source before hipMemcpyAsync returns (not so for a
+      // caller's table, which kernels fill)
       if (e == hipSuccess)
         e = hipMemcpyAsync(owned, host.data(), host.size(), hipMemcpyHostToDevice, st);
     }

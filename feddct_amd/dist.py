@@ -514,8 +514,9 @@ class StripedAggregator:
                 raise ValueError(f"{len(weights)} weights for {b - a} clients")
             send = []
             for j, t in enumerate(local32):
-                wj = torch.tensor(float(np.float32(weights[j])), device=t.device)
-                send.append(t * wj)
+                # (a Python scalar: a device tensor made from one is a blocking
+                # upload, a stream synchronisation per client)
+                send.append(t * float(np.float32(weights[j])))
             wfull = [1.0] * self.n_total
             for j in range(b - a):
                 wfull[a + j] = float(np.float32(weights[j]))
@@ -722,7 +723,10 @@ class ChainAggregator:
             for j, t in enumerate(local32):
                 v = t[self.tidx]
                 if weights is not None:
-                    v = v * torch.tensor(float(np.float32(weights[j])), device=v.device)
+                    # a Python scalar, not a device tensor made from one: that
+                    # is a blocking upload, one stream synchronisation per client
+                    # (the product is the same fp32 multiply by the fp32 weight)
+                    v = v * float(np.float32(weights[j]))
                 self.stack32[j, :self.T] = v
         for j, t in enumerate(local64):
             self.stack64[j].copy_(t)

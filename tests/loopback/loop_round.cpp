@@ -52,6 +52,14 @@
 // FA_LOOP_WEIGHTS=path: round 0's n float32 weights.
 // FA_LOOP_DUMP=path: the first result rank's out32 then out64, raw, of the
 // last case's last round.
+// FA_LOOP_GATE_MS=ms (threads model, scripts): after every round but the last,
+// each rank queues a one-thread spin kernel of that length on its stream
+// BEFORE it refills its client buckets for the next round, and issues the next
+// round at once: every launch of that round is queued while its inputs still
+// hold the previous round's data, so work that the executor puts on its
+// communication stream without joining the caller's stream reads stale values
+// and the round's result is wrong.  A round whose call returns after its gate
+// has ended fails the case ("gate too short / call blocked the host").
 // FA_LOOP_PROFILE=1 (threads model): every rank's communicator profiles its
 // rounds (fa_comm_set_profile) and the line carries rank 0's
 // fa_round_plan_profile of the last.
@@ -171,6 +179,17 @@ bool parse_case(const std::string& s, Case* c) {
     }                                                                       \
   } while (0)
 
+// FA_LOOP_GATE_MS: one thread spins until `ticks` of the constant-rate wall
+// clock have passed.  `cap` bounds the trips as well (a trip is a clock read:
+// tens of nanoseconds at least, so 2^20 trips per millisecond asked for is far
+// beyond the gate and still well under a second per 10 ms), so the kernel ends
+// whatever the clock or its reported rate do.
+__global__ void gate_kernel(long long ticks, long long cap) {
+  const long long t0 = wall_clock64();
+  for (long long i = 0; i < cap && wall_clock64() - t0 < ticks; ++i) {
+  }
+}
+
 // Words of a[0..n) that differ from b's (the inputs' check: bit for bit).
 __global__ void count_diff_kernel(const uint32_t* a, const uint32_t* b, int64_t n,
                                   unsigned long long* bad) {
@@ -198,6 +217,8 @@ struct Rank {
   int64_t* out64 = nullptr;
   float* save32 = nullptr;      // [rounds][F]: each round's result
   int64_t* save64 = nullptr;    // [rounds][I]
+  hipEvent_t gate_end = nullptr;  // FA_LOOP_GATE_MS: the end of the last gate on st
+  bool gated = false;
   int rc = 0;
   std::string err;
   fa_round_profile prof{};
@@ -417,6 +438,14 @@ bool run_case(const Case& c, const Layout& L) {
   };
   // after: keep the result, then overwrite the rank's own inputs in place with
   // the next round's
+  const int gate_ms = getenv("FA_LOOP_GATE_MS") ? atoi(getenv("FA_LOOP_GATE_MS")) : 0;
+  int clock_khz = 0;
+  if (gate_ms > 0 &&
+      hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, 0) != hipSuccess)
+    return refuse("no wall clock rate");
+  if (gate_ms > 0 && (c.model != "threads" || gate_ms > 200))
+    return refuse("FA_LOOP_GATE_MS: threads model only (its check runs between a rank's "
+                  "rounds), at most 200");
   auto after = [&](Rank& k, int rd) {
     const int r = (int)(&k - R.data());
     if (c.rounds[rd].root < 0 || c.rounds[rd].root == r) {
@@ -425,6 +454,15 @@ bool run_case(const Case& c, const Layout& L) {
           hipMemcpyAsync(k.save64 + (size_t)rd * I, k.out64, I * 8, hipMemcpyDeviceToDevice,
                          k.st) != hipSuccess)
         return -1;
+    }
+    if (rd + 1 < K && gate_ms > 0) {
+      if (!k.gate_end && hipEventCreateWithFlags(&k.gate_end, hipEventDisableTiming) != hipSuccess)
+        return -1;
+      hipLaunchKernelGGL(gate_kernel, dim3(1), dim3(1), 0, k.st, (long long)gate_ms * clock_khz,
+                         (long long)gate_ms << 20);
+      if (hipGetLastError() != hipSuccess || hipEventRecord(k.gate_end, k.st) != hipSuccess)
+        return -1;
+      k.gated = true;
     }
     if (rd + 1 < K)
       for (size_t j = 0; j < k.c32.size(); ++j)
@@ -458,14 +496,20 @@ bool run_case(const Case& c, const Layout& L) {
             std::vector<Rank*> rk{&k};
             k.rc = before(k, rd, &io[0]);
             if (!k.rc) k.rc = run_round(c, L, c.rounds[rd].root, rk, plans, io);
+            if (!k.rc && k.gated && hipEventQuery(k.gate_end) != hipErrorNotReady) {
+              k.rc = -1;
+              k.err = "round " + std::to_string(rd + 1) + ": gate too short / call blocked the host";
+            }
             if (!k.rc) k.rc = after(k, rd);
           }
           if (!k.rc && prof && k.plan) {
             k.rc = fa_round_plan_profile(k.plan, &k.prof);
             k.has_prof = k.rc == 0;
           }
-          if (k.rc) k.err = fa_last_error();
+          if (k.rc && k.err.empty()) k.err = fa_last_error();
           if (k.st) (void)hipStreamSynchronize(k.st);
+          if (k.gate_end) (void)hipEventDestroy(k.gate_end);
+          k.gate_end = nullptr;
         });
       for (auto& t : th) t.join();
     }

@@ -87,15 +87,18 @@ def _digest_params(layout, parts):
 
 
 def _run(layout, cases, tmp_path, timeout=240, params=None, dump=None, profile=False,
-         clients=None, weights=None):
+         clients=None, weights=None, gate_ms=0):
     """``clients`` / ``weights``: files of round 0's fp32 client buckets and
-    weights (FA_LOOP_CLIENTS / FA_LOOP_WEIGHTS) instead of the generator's."""
+    weights (FA_LOOP_CLIENTS / FA_LOOP_WEIGHTS) instead of the generator's;
+    ``gate_ms``: FA_LOOP_GATE_MS, every later round issued behind a gate."""
     assert os.path.exists(DRIVER), "tests/loopback/loop_round is not built (run build())"
     lf = str(tmp_path / "layout.txt")
     _write_layout(layout, lf, params)
     env = dict(os.environ, FA_LOOP_TIMEOUT_S="30")
     if profile:
         env["FA_LOOP_PROFILE"] = "1"
+    if gate_ms:
+        env["FA_LOOP_GATE_MS"] = str(gate_ms)
     if dump:
         env["FA_LOOP_DUMP"] = dump
     if clients:
@@ -409,6 +412,25 @@ def test_loopback_rounds_on_one_plan(tmp_path, form):
     still hold the last round's data afterwards."""
     cases = ROUND_CASES[form]
     _check_rounds(_run(_small_layout(), cases, tmp_path), cases)
+
+
+GATED_CASES = [c for form in sorted(ROUND_CASES) for c in ROUND_CASES[form][:1]] + [
+    ROUND_CASES["sharded"][1], ROUND_CASES["multi"][2]]
+
+
+def test_loopback_rounds_behind_a_gate(tmp_path):
+    """Stream order of the executor (fedcomm.hip) with two and more ranks: one
+    scripted case per round form, every rank's later rounds issued while a
+    spin kernel still holds back, on the rank's own stream, the writes of that
+    round's client data (FA_LOOP_GATE_MS, loop_round.cpp).  Whatever the
+    executor queues for such a round — the exchanges, the /N finish and the
+    int64 gather on its communication stream, the kernels on the caller's —
+    runs in stream order behind those writes only through its entry join of
+    the two streams; without it the communication stream reads the previous
+    round's data and the round's result is wrong.  The driver fails a round
+    whose call returned after its gate had ended."""
+    assert all(":threads:" in c for c in GATED_CASES) and len(GATED_CASES) == 7
+    _check_rounds(_run(_small_layout(), GATED_CASES, tmp_path, gate_ms=30), GATED_CASES)
 
 
 def test_loopback_rounds_deep_blocked(tmp_path):
