@@ -59,6 +59,7 @@ EXPORTS = [
     "fa_norm_plan_create", "fa_norm_plan_destroy", "fa_prox_norms", "fa_prox_grad",
     "fa_prox_grad_ex", "fa_prox_norms_elem", "fa_prox_grad_elem",
     "fa_read_probe_f32", "fa_write_probe_f32", "fa_tune_prox_store", "fa_tune_prox_cpw", "fa_chain_levels", "fa_reduce_chain", "fa_torch_gpu_config",
+    "fa_reduce_chain_elem",
     "fa_plan_create_order", "fa_table_bytes", "fa_reduce_tab",
     "fa_plan_balance_host", "fa_plan_launch_shape", "fa_plan_launch_form",
     "fa_plan_create_elem", "fa_plan_build_host_elem", "fa_plan_elem",
@@ -157,6 +158,8 @@ def _load():
         "fa_plan_build_order_host_elem": (_I, [_P, _I, _I64, _P, _I, _I64, _I, _I, ctypes.c_uint,
                                                _I, _I, _P, _P, _I, _P, ctypes.POINTER(_I)]),
         "fa_reduce_chain": (_I, [_P, _P, _I, _P, ctypes.POINTER(FaChain), _P, ctypes.c_uint, _P]),
+        "fa_reduce_chain_elem": (_I, [_P, _P, _I, _P, ctypes.POINTER(FaChain), _P, ctypes.c_uint,
+                                      _P]),
         "fa_norm_plan_create": (_I, [_P, _I, _I64, ctypes.POINTER(_P)]),
         "fa_norm_plan_destroy": (_I, [_P]),
         "fa_prox_norms": (_I, [_P, _P, _P, _P, _P, _P]),

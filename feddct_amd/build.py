@@ -10,9 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # in parallel (one unit held them all: 5 minutes of device compilation)
 SRCS = [os.path.join(HERE, "csrc", f) for f in
         ("fedagg.hip", "fedagg_k1.hip", "fedagg_k2.hip", "fedagg_k2w.hip", "fedagg_k4.hip",
-         "fedagg_h16.hip", "fedagg_tgpu16.hip", "prox.hip", "prox_h16.hip", "plan_host.cpp")]
+         "fedagg_h16.hip", "fedagg_chain16.hip", "fedagg_tgpu16.hip", "prox.hip", "prox_h16.hip", "plan_host.cpp")]
 HEADERS = [os.path.join(HERE, "csrc", h) for h in
-           ("common.h", "err.h", "tiles.h", "plan_host.h", "reduce_impl.h", "h16.h", "tgpu16.h", "conv16.h",
+           ("common.h", "err.h", "tiles.h", "plan_host.h", "reduce_impl.h", "h16.h", "h16_vec.h", "tgpu16.h", "conv16.h",
             "prox_plan.h")] + \
           [os.path.join(HERE, "..", "include", "fedagg.h")]
 DEPS = SRCS + HEADERS

@@ -19,7 +19,9 @@ Every native round runs on fp32 buckets: on a native 16-bit layout
 before touching the library (they used to hand 16-bit buckets to fp32
 kernels).  The 16-bit striped round runs over torch.distributed
 (``dist.StripedAggregator``); ``describe`` and ``round_model``
-give its schedule and modelled cost.
+give its schedule and modelled cost, and with ``chain16=True`` those of the
+16-bit chained round (``dist.ChainAggregator(native16=True)``),
+which ``multi_select(..., chain16=True)`` weighs against the striped one.
 
 No fallback: loading raises if libfedagg_comm.so is missing.
 """
@@ -52,7 +54,8 @@ COMM_EXPORTS = ["fa_comm_unique_id", "fa_comm_init_rank", "fa_comm_init", "fa_co
                 "fa_mean_f32_multi_ex", "fa_stripe_plan_create_ex", "fa_multi_select_layout",
                 "fa_multi_plan_chunks", "fa_round_model", "fa_comm_set_profile",
                 "fa_round_plan_profile", "fa_model_constants", "fa_describe_round_elem",
-                "fa_round_model_elem"]
+                "fa_round_model_elem", "fa_describe_round_opts", "fa_round_model_opts",
+                "fa_multi_select_layout_elem"]
 
 FA_XCHG_REDUCE, FA_XCHG_RS_GATHER = 0, 1
 FA_MODE_SHARDED, FA_MODE_STRIPED, FA_MODE_CHAINED, FA_MODE_BLOCKED = 0, 1, 2, 3
@@ -60,6 +63,7 @@ MODE_NAMES = {FA_MODE_SHARDED: "e1", FA_MODE_STRIPED: "striped", FA_MODE_CHAINED
               FA_MODE_BLOCKED: "blocked"}
 MODE_IDS = {v: k for k, v in MODE_NAMES.items()}
 FA_MULTI_EXACT, FA_MULTI_REASSOCIATE, FA_MULTI_ROOT_ALL = 0, 1, 2
+FA_ROUND_CHAIN16 = 1       # round option: the chained round on a 16-bit bucket
 # the cost model's constants (fedagg_comm.h FA_MODEL_*)
 MODEL_LINK_GBPS, MODEL_HBM_GBPS, MODEL_GROUP_US, MODEL_KERNEL_US = 64.0, 6500.0, 15.0, 3.0
 # The e1 round's distance from the exact result, measured r04 (2 ranks x 20
@@ -160,6 +164,11 @@ def _load():
     # the element-aware host entries: the fp32 signature plus the element type
     sig["fa_describe_round_elem"] = sig["fa_describe_round"] + [_I]
     sig["fa_round_model_elem"] = sig["fa_round_model"] + [_I]
+    # ... plus the round options (FA_ROUND_*)
+    sig["fa_describe_round_opts"] = sig["fa_describe_round_elem"] + [ctypes.c_uint]
+    sig["fa_round_model_opts"] = sig["fa_round_model_elem"] + [ctypes.c_uint]
+    sig["fa_multi_select_layout_elem"] = sig["fa_multi_select_layout"][:10] + \
+        [_I, ctypes.c_uint] + sig["fa_multi_select_layout"][10:]
     for name, args in sig.items():
         fn = getattr(lib, name)
         fn.restype = _I
@@ -182,15 +191,27 @@ def _mflags(exact: bool, root_all: bool) -> int:
 
 
 def multi_select(counts: Sequence[int], exact: bool = True, layout: Optional[BucketLayout] = None,
-                 root_all: bool = False, detail: bool = False):
+                 root_all: bool = False, detail: bool = False, chain16: bool = False):
     """The round form the default entry takes for these shard counts (host
     only): "blocked", "chained", "striped", or "e1" when ``exact=False`` —
     the exact form with the lowest modelled time (fa_multi_select_layout) on
     ``layout`` (None: fa_multi_select's nominal 2^24-float layout).
     ``root_all``: the result on every rank (FA_MULTI_ROOT_ALL) rather than on
-    the last rank holding slots.  ``detail``: (form, nchunks, model_us)."""
+    the last rank holding slots.  ``detail``: (form, nchunks, model_us).
+    ``chain16``: on a native 16-bit ``layout``, the better of the chained and
+    the striped round (fa_multi_select_layout_elem with FA_ROUND_CHAIN16)
+    instead of the fp32 bucket's choice."""
     c = _counts(counts)
     m, k, us = _I(), _I(), ctypes.c_double()
+    if chain16:
+        elem = None if layout is None else layout_elem(layout)
+        if elem is None:
+            raise ValueError("chain16 names the chained round on a native 16-bit layout")
+        _lib.check(lib().fa_multi_select_layout_elem(
+            len(counts), c, *_layout_args(layout), _lib.FA_PLAN_GAPS_ARE_PADDING,
+            _mflags(exact, root_all), elem, FA_ROUND_CHAIN16, ctypes.byref(m), ctypes.byref(k),
+            ctypes.byref(us)), "fa_multi_select_layout_elem")
+        return (MODE_NAMES[m.value], k.value, us.value) if detail else MODE_NAMES[m.value]
     if layout is None:
         _lib.check(lib().fa_multi_select(len(counts), c, _mflags(exact, root_all),
                                          ctypes.byref(m)), "fa_multi_select")
@@ -215,16 +236,22 @@ def model_constants() -> dict:
 
 
 def round_model(mode: int, layout: BucketLayout, counts: Sequence[int], nchunks: int = 0,
-                exchange: int = FA_XCHG_REDUCE, root: int = 0, weighted: bool = False) -> dict:
+                exchange: int = FA_XCHG_REDUCE, root: int = 0, weighted: bool = False,
+                chain16: bool = False) -> dict:
     """The cost model's view of one round (fa_round_model, host only): the
     modelled time in microseconds, the largest byte count on one link
-    direction, the largest per-rank HBM byte count, group and step counts."""
+    direction, the largest per-rank HBM byte count, group and step counts.
+    ``chain16``: the chained round on a native 16-bit layout
+    (fa_round_model_opts with FA_ROUND_CHAIN16)."""
     out = FaRoundCost()
     args = (int(mode), len(counts), _counts(counts), *_layout_args(layout), int(nchunks),
             int(exchange), _lib.FA_PLAN_GAPS_ARE_PADDING, int(root), int(bool(weighted)),
             ctypes.byref(out))
     elem = layout_elem(layout)
-    if elem is None:
+    if chain16:
+        _lib.check(lib().fa_round_model_opts(*args, _lib.FA_ELEM_F32 if elem is None else elem,
+                                             FA_ROUND_CHAIN16), "fa_round_model_opts")
+    elif elem is None:
         _lib.check(lib().fa_round_model(*args), "fa_round_model")
     else:   # a native 16-bit layout: 2 bytes per element on the links and in HBM
         _lib.check(lib().fa_round_model_elem(*args, elem), "fa_round_model_elem")
@@ -252,16 +279,21 @@ def _counts(counts: Sequence[int]):
 
 def describe(mode: int, layout: BucketLayout, counts: Sequence[int], rank: int,
              nchunks: int = 8, exchange: int = FA_XCHG_REDUCE, root: int = 0,
-             weighted: bool = False) -> List[dict]:
+             weighted: bool = False, chain16: bool = False) -> List[dict]:
     """Rank ``rank``'s schedule of one round (fa_describe_round): the exact
     list of exchanges and kernels the native executor issues, computed on the
     host (no GPU, no communicator).  A native 16-bit layout: the 16-bit
-    round's (fa_describe_round_elem; offsets and counts in 16-bit elements)."""
+    round's (fa_describe_round_elem; offsets and counts in 16-bit elements).
+    ``chain16``: the chained round on a native 16-bit layout
+    (fa_describe_round_opts with FA_ROUND_CHAIN16), mean or weighted."""
     n = _I()
     args = (mode, len(counts), rank, _counts(counts), *_layout_args(layout), int(nchunks),
             int(exchange), _lib.FA_PLAN_GAPS_ARE_PADDING, int(root), int(bool(weighted)))
     elem = layout_elem(layout)
-    if elem is None:
+    if chain16:
+        fn, name = lib().fa_describe_round_opts, "fa_describe_round_opts"
+        tail = (_lib.FA_ELEM_F32 if elem is None else elem, FA_ROUND_CHAIN16)
+    elif elem is None:
         fn, tail, name = lib().fa_describe_round, (), "fa_describe_round"
     else:
         fn, tail, name = lib().fa_describe_round_elem, (elem,), "fa_describe_round_elem"

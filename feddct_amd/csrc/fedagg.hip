@@ -1804,56 +1804,65 @@ int fa_reduce_tab(const fa_plan* plan, const float* const* c32, const int64_t* c
   return FA_OK;
 }
 
-int fa_reduce_chain(const fa_plan* plan, const float* const* c32, int n, const float* weights,
-                    const fa_chain* ch, float* out32, unsigned flags, void* stream) {
-  if (!plan || !ch) return set_err(FA_E_INVAL, "fa_reduce_chain: plan/chain is NULL");
-  if (flags & ~FA_F_SUM_ONLY) return set_err(FA_E_INVAL, "fa_reduce_chain: bad flags");
+namespace {
+// fa_reduce_chain (`who` names it; fp32 plans) and fa_reduce_chain_elem's
+// 16-bit path (`h16`: an h16-family plan, the kernels of fedagg_chain16.hip):
+// one set of checks in one order, every refusal before anything is launched.
+int reduce_chain(const char* who, bool h16, const fa_plan* plan, const void* const* c, int n,
+                 const float* weights, const fa_chain* ch, void* out, unsigned flags,
+                 void* stream) {
+  if (!plan || !ch) return set_err(FA_E_INVAL, "%s: plan/chain is NULL", who);
+  if (flags & ~FA_F_SUM_ONLY) return set_err(FA_E_INVAL, "%s: bad flags", who);
   const int nt = ch->n_total;
   if (nt < 1 || nt > FA_MAX_CLIENTS)
-    return set_err(FA_E_RANGE, "fa_reduce_chain: n_total=%d outside 1..%d", nt, FA_MAX_CLIENTS);
+    return set_err(FA_E_RANGE, "%s: n_total=%d outside 1..%d", who, nt, FA_MAX_CLIENTS);
   if (n < 1 || ch->row0 < 0 || ch->row0 + n > nt)
-    return set_err(FA_E_INVAL, "fa_reduce_chain: rows [%d,+%d) outside the %d-row reduction",
-                   ch->row0, n, nt);
-  if (plan->elem != FA_ELEM_F32)
-    return set_err(FA_E_INVAL, "fa_reduce_chain: not defined for a 16-bit plan (the state planes "
-                               "are fp32; chain fp32 buckets)");
+    return set_err(FA_E_INVAL, "%s: rows [%d,+%d) outside the %d-row reduction", who, ch->row0, n,
+                   nt);
+  if (!h16 && plan->elem != FA_ELEM_F32)
+    return set_err(FA_E_INVAL, "%s: not defined for a 16-bit plan (the state planes "
+                               "are fp32; chain fp32 buckets)", who);
+  if (h16 && plan->family != FaFamily::kH16)
+    return set_err(FA_E_INVAL, "%s: not defined for a torch-GPU-order plan (the chain carries "
+                               "the cascade of torch's CPU order)", who);
+  if (h16 && (flags & FA_F_SUM_ONLY) && plan->out_elem != FA_ELEM_F32)
+    return set_err(FA_E_INVAL, "%s: FA_F_SUM_ONLY is not defined for a 16-bit result (the "
+                               "ordered fp32 sum has no 16-bit slot to go to)", who);
   if (plan->has64 || plan->info.ntiles_tail > 0)
     return set_err(FA_E_INVAL,
-                   "fa_reduce_chain: the plan holds scalar tiles (tails, M==1, int64); chain "
-                   "plans carry vector tiles only (scalar columns travel raw, fedagg_comm.h)");
+                   "%s: the plan holds scalar tiles (tails, M==1, int64); chain "
+                   "plans carry vector tiles only (scalar columns travel raw, fedagg_comm.h)",
+                   who);
   const unsigned lin = fa_chain_levels(ch->row0, nt);
   const unsigned lout = fa_chain_levels(ch->row0 + n, nt);
   if (lin && !ch->state_in)
-    return set_err(FA_E_INVAL, "fa_reduce_chain: rows 0..%d-1 leave a state: state_in required",
-                   ch->row0);
-  if (!ch->state_out && !out32)
-    return set_err(FA_E_INVAL, "fa_reduce_chain: need state_out or out32");
+    return set_err(FA_E_INVAL, "%s: rows 0..%d-1 leave a state: state_in required", who, ch->row0);
+  if (!ch->state_out && !out) return set_err(FA_E_INVAL, "%s: need state_out or out32", who);
   if (ch->state_out && ch->row0 + n == nt)
-    return set_err(FA_E_INVAL, "fa_reduce_chain: the last segment finishes (state_out NULL)");
+    return set_err(FA_E_INVAL, "%s: the last segment finishes (state_out NULL)", who);
   if (!ch->state_out && ch->row0 + n != nt)
-    return set_err(FA_E_INVAL, "fa_reduce_chain: only the last segment (rows ..%d) finishes",
-                   nt - 1);
+    return set_err(FA_E_INVAL, "%s: only the last segment (rows ..%d) finishes", who, nt - 1);
   const bool st = ch->state_in || ch->state_out;
   if (st && (ch->plane < plan->info.f32_numel || ch->plane % 4))
-    return set_err(FA_E_INVAL, "fa_reduce_chain: plane=%lld must be >= %lld and a multiple of 4",
+    return set_err(FA_E_INVAL, "%s: plane=%lld must be >= %lld and a multiple of 4", who,
                    (long long)ch->plane, (long long)plan->info.f32_numel);
   if ((ch->state_in && !aligned16(ch->state_in)) || (ch->state_out && !aligned16(ch->state_out)) ||
-      (out32 && !aligned16(out32)))
-    return set_err(FA_E_ALIGN, "fa_reduce_chain: state/out buffers not 16-B aligned");
+      (out && !aligned16(out)))
+    return set_err(FA_E_ALIGN, "%s: state/out buffers not 16-B aligned", who);
   if (plan->info.ntiles == 0) return FA_OK;
-  if (!c32) return set_err(FA_E_INVAL, "fa_reduce_chain: fp32 buckets required");
+  if (!c) return set_err(FA_E_INVAL, "%s: %s buckets required", who, h16 ? "16-bit" : "fp32");
   for (int i = 0; i < n; ++i)
-    if (!c32[i] || !aligned16(c32[i]))
-      return set_err(FA_E_ALIGN, "fa_reduce_chain: client %d bucket NULL or not 16-B aligned", i);
+    if (!c[i] || !aligned16(c[i]))
+      return set_err(FA_E_ALIGN, "%s: client %d bucket NULL or not 16-B aligned", who, i);
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev != plan->device)
-    return set_err(FA_E_INVAL, "fa_reduce_chain: plan built on device %d, current device %d",
+    return set_err(FA_E_INVAL, "%s: plan built on device %d, current device %d", who,
                    plan->device, dev);
   ReduceArgs a;
   memset(&a, 0, sizeof a);
   a.tiles = plan->d_tiles;
-  a.out32 = out32;
+  a.out32 = (float*)out;  // (a 16-bit plan: the 16-bit result bucket)
   a.n = n;
   a.n_total = nt;
   a.row0 = ch->row0;
@@ -1866,12 +1875,32 @@ int fa_reduce_chain(const fa_plan* plan, const float* const* c32, int n, const f
   a.ntiles = plan->nt;
   hipStream_t s = (hipStream_t)stream;
   ClientTable tab{s};
-  hipError_t e = tab.fill(a, c32, nullptr, n, weights, nullptr);
+  hipError_t e = tab.fill(a, (const float* const*)c, nullptr, n, weights, nullptr);
   if (e != hipSuccess)
-    return set_err(FA_E_HIP, "fa_reduce_chain: client pointer table: %s", hipGetErrorString(e));
-  e = tab.done(launch_chain(a, a.ntiles, plan->vec_u, s));
-  if (e != hipSuccess) return set_err(FA_E_HIP, "chain launch: %s", hipGetErrorString(e));
+    return set_err(FA_E_HIP, "%s: client pointer table: %s", who, hipGetErrorString(e));
+  e = tab.done(h16 ? fa_chain16::launch(a, a.ntiles, plan->elem, plan->vec_u, weights != nullptr,
+                                        plan->out_elem == FA_ELEM_F32, s)
+                   : launch_chain(a, a.ntiles, plan->vec_u, s));
+  if (e != hipSuccess)
+    return set_err(FA_E_HIP, "%s: %s", h16 ? "16-bit chain launch" : "chain launch",
+                   hipGetErrorString(e));
   return FA_OK;
+}
+}  // namespace
+
+int fa_reduce_chain(const fa_plan* plan, const float* const* c32, int n, const float* weights,
+                    const fa_chain* ch, float* out32, unsigned flags, void* stream) {
+  return reduce_chain("fa_reduce_chain", false, plan, (const void* const*)c32, n, weights, ch,
+                      out32, flags, stream);
+}
+
+int fa_reduce_chain_elem(const fa_plan* plan, const void* const* c, int n, const float* weights,
+                         const fa_chain* ch, void* out, unsigned flags, void* stream) {
+  // an fp32 plan (and a NULL one's refusal): fa_reduce_chain exactly
+  if (!plan || plan->elem == FA_ELEM_F32)
+    return fa_reduce_chain(plan, (const float* const*)c, n, weights, ch, (float*)out, flags,
+                           stream);
+  return reduce_chain("fa_reduce_chain_elem", true, plan, c, n, weights, ch, out, flags, stream);
 }
 
 int fa_mean_f32(const float* const* clients, int n, int64_t numel, float* out,

@@ -35,91 +35,16 @@
 #include "common.h"
 #include "conv16.h"
 #include "h16.h"
+#include "h16_vec.h"
 
 namespace fa_h16 {
 using namespace fa_k;
 
-typedef __attribute__((address_space(1))) const u4 gcu4;
-
-// (widen, widen2, narrow, narrow2, widen8, narrow8: conv16.h, shared with
-// prox_h16.hip)
-
-// 16-B non-temporal load of vector `vidx` (8 elements) past a uniform base.
-__device__ __forceinline__ u4 ldu4(const uint16_t* base, uint32_t vidx) {
-  return __builtin_nontemporal_load((gcu4*)base + vidx);
-}
-// The result store: a buffer store with the sc1 policy bit, the fp32
-// reduce's (reduce_impl.h st_out: the broadcast reads the result next).
-__device__ __forceinline__ void st_sc1(uint16_t* base, uint32_t vidx, u4 v) {
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc(base, (short)0, 0x7fffffff, 0x00020000);
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)(16 * vidx), 0, 16);
-}
-// The wide result store (an fp32 result bucket): one 16-B store of fp32 at
-// byte offset `off` past a uniform base, the same policy.
-__device__ __forceinline__ void st_sc1_f4(float* base, uint32_t off, f4 v) {
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc(base, (short)0, 0x7fffffff, 0x00020000);
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, 16);
-}
-__device__ __forceinline__ f4 shfl4(f4 v, int src) {
-  return f4{__shfl(v.x, src, 64), __shfl(v.y, src, 64), __shfl(v.z, src, 64),
-            __shfl(v.w, src, 64)};
-}
+// (ldu4, st_sc1, st_sc1_f4, shfl4, the pointer sources cptr16 / cw16 and the
+// client loop clients16: h16_vec.h, shared with the chain segments of
+// fedagg_chain16.hip)
 
 // --------------------------------------------------------- vector tiles ----
-// Client i's bucket and weight through scalar loads only: the kernarg arrays
-// (n <= kInline) or the device table through the constant address space.
-template <bool TAB>
-__device__ __forceinline__ const uint16_t* cptr16(KArgs& a, int i) {
-  if constexpr (TAB) return (const uint16_t*)((const FA_CONST f32p*)a.tab32)[i];
-  else return (const uint16_t*)a.c32[i];
-}
-template <bool TAB>
-__device__ __forceinline__ float cw16(KArgs& a, int i) {
-  if constexpr (TAB) return ((const FA_CONST float*)a.tabw)[i];
-  else return a.w[i];
-}
-
-// The clients in slot order, the next client's loads issued before the
-// current client's adds.  Lane vector u holds columns 8 * vi[u] .. + 7 in
-// accumulators 2u (first four) and 2u + 1.
-template <int EL, int U, bool FULL, bool W, bool TAB>
-__device__ __forceinline__ void clients16(KArgs& a, Acc<2 * U, true>& A, int n, int64_t start,
-                                          const uint32_t (&vi)[U], const bool (&ok)[U], int lp,
-                                          int mask) {
-  const u4 zero = u4{0u, 0u, 0u, 0u};
-  u4 cur[U], nxt[U];
-  {
-    const uint16_t* p = cptr16<TAB>(a, 0) + start;
-#pragma unroll
-    for (int u = 0; u < U; ++u) cur[u] = (FULL || ok[u]) ? ldu4(p, vi[u]) : zero;
-  }
-  for (int b = 0; b < n; ++b) {
-    if (b + 1 < n) {
-      const uint16_t* p = cptr16<TAB>(a, b + 1) + start;
-#pragma unroll
-      for (int u = 0; u < U; ++u) nxt[u] = (FULL || ok[u]) ? ldu4(p, vi[u]) : zero;
-    }
-    float wb = 0.f;
-    if constexpr (W) wb = cw16<TAB>(a, b);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      f4 x0, x1;
-      widen8<EL>(cur[u], &x0, &x1);
-      if constexpr (W) {
-        x0 = mul4s(x0, wb);
-        x1 = mul4s(x1, wb);
-      }
-      A.l0[2 * u] = add4(A.l0[2 * u], x0);
-      A.l0[2 * u + 1] = add4(A.l0[2 * u + 1], x1);
-    }
-    promote<2 * U, true>(A, b + 1, lp, mask);
-#pragma unroll
-    for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-  }
-}
-
 template <int EL, int U, bool FULL, bool W, bool WIDE>
 __device__ __forceinline__ void tile_vec16(KArgs& a, int64_t start, int count) {
   const int n = a.n;
@@ -138,8 +63,8 @@ __device__ __forceinline__ void tile_vec16(KArgs& a, int64_t start, int count) {
 #pragma unroll
   for (int j = 0; j < 2 * U; ++j)
     A.l0[j] = A.l1[j] = A.l2[j] = A.l3[j] = f4{0.f, 0.f, 0.f, 0.f};
-  if (n <= kInline) clients16<EL, U, FULL, W, false>(a, A, n, start, vi, ok, lp, mask);
-  else clients16<EL, U, FULL, W, true>(a, A, n, start, vi, ok, lp, mask);
+  if (n <= kInline) clients16<EL, U, FULL, W, false>(a, A, n, start, vi, ok, lp, mask, 0);
+  else clients16<EL, U, FULL, W, true>(a, A, n, start, vi, ok, lp, mask, 0);
   const float fn = (float)n;
   if constexpr (WIDE) {
     // A lane's 8 fp32 results are 32 B; stored from the lane that summed

@@ -29,3 +29,13 @@ hipError_t bcast_narrow(const fa_k::ReduceArgs& a, int n, int elem, int64_t f32_
 // (fa_narrow_f32): both 16-B aligned, any numel.
 hipError_t narrow_range(const float* src, void* dst, int elem, int64_t numel, hipStream_t st);
 }  // namespace fa_h16
+
+namespace fa_chain16 {
+// A chain segment over 16-bit buckets (fedagg_chain16.hip), one workgroup per
+// vector tile of the table in `a`: rows a.row0 .. a.row0 + a.n - 1 of an
+// a.n_total-row reduction, from the fp32 state planes a.st_in / a.lev_in to
+// a.st_out / a.lev_out, or (a.st_out NULL) finished into a.out32 — the 16-bit
+// bucket, or with `wide` the fp32 one.
+hipError_t launch(const fa_k::ReduceArgs& a, int ntiles, int elem, int u, bool weighted, bool wide,
+                  hipStream_t st);
+}  // namespace fa_chain16

@@ -96,6 +96,25 @@ int check_round_elem(const char* who, int elem, int mode, int weighted) {
   return FA_OK;
 }
 
+// FA_ROUND_CHAIN16: the chained round on a 16-bit bucket, mean or weighted;
+// nothing else takes the bit.  Without a bit: check_round_elem.
+int check_round_opts(const char* who, int elem, int mode, int weighted, unsigned ropts) {
+  if (ropts & ~(unsigned)FA_ROUND_CHAIN16)
+    return set_err(FA_E_INVAL, "%s: unknown round options 0x%x", who, ropts);
+  if (!(ropts & FA_ROUND_CHAIN16)) return check_round_elem(who, elem, mode, weighted);
+  if (elem != FA_ELEM_F16 && elem != FA_ELEM_BF16)
+    return set_err(FA_E_INVAL,
+                   "%s: FA_ROUND_CHAIN16 with elem=%d: the option names the chained round on an "
+                   "fp16 / bf16 bucket (an fp32 bucket chains without it)",
+                   who, elem);
+  if (mode != FA_MODE_CHAINED)
+    return set_err(FA_E_INVAL,
+                   "%s: FA_ROUND_CHAIN16 with mode %d: the option names the chained round "
+                   "(FA_MODE_CHAINED) only",
+                   who, mode);
+  return FA_OK;
+}
+
 namespace {
 
 // k contiguous groups of sorted tiles with equal shares of the elements, cut
@@ -281,7 +300,12 @@ void sched_striped(const Geo& g, const std::vector<std::vector<int64_t>>& clo, i
   S->next();
 }
 
-void sched_chained(const Geo& g, const ChainGeo& cg, int root, Sched* S) {
+// A 16-bit round (FA_ROUND_CHAIN16): CLIENT, OUT, FIN and the stacked scalar
+// columns hold 16-bit elements, the STATE planes fp32.  Weighted, the chain
+// kernels multiply by the local weights and the scalar columns travel raw, so
+// the result ranks need every rank's weights: one more all-gather (STACK /
+// GATHER index 2, nmax floats per rank) in the scalar columns' group.
+void sched_chained(const Geo& g, const ChainGeo& cg, int root, bool weighted, Sched* S) {
   const int me = g.rank, F = cg.finisher;
   const bool result = root < 0 || root == me;
   // the raw scalar columns first: their gather overlaps the chain
@@ -296,6 +320,8 @@ void sched_chained(const Geo& g, const ChainGeo& cg, int root, Sched* S) {
     if (i64)
       S->add(FA_X_ALLGATHER, -1, FA_B_STACK, 1, FA_B_GATHER, 1, 0,
              (int64_t)g.nmax * g.i64_numel);
+    if (weighted && g.elem != FA_ELEM_F32 && cg.t32_width)
+      S->add(FA_X_ALLGATHER, -1, FA_B_STACK, 2, FA_B_GATHER, 2, 0, (int64_t)g.nmax);
     S->next();
   }
   if (me <= F) {
@@ -471,7 +497,7 @@ void chain_geo(const Geo& g, int nchunks, ChainGeo* cg, std::vector<fa_tile_desc
   cg->t32_width = (int64_t)tidx->size();
   cg->t32_row = (cg->t32_width + 63) / 64 * 64;
   cg->range.clear();
-  cut_tiles(*vec, nchunks, cut);
+  cut_tiles(*vec, nchunks, cut, cut_align(g.elem));
   std::vector<size_t> keep(1, 0);
   for (int c = 0; c < nchunks; ++c) {
     if ((*cut)[c] == (*cut)[c + 1]) continue;
@@ -645,7 +671,7 @@ std::vector<fa_xfer> schedule(const RoundGeo& p, int root, bool weighted) {
   Sched S;
   if (p.mode == FA_MODE_SHARDED) sched_sharded(p.g, p.range, p.xchg, root, weighted, &S);
   else if (p.mode == FA_MODE_STRIPED) sched_striped(p.g, p.clo, root, weighted, &S);
-  else if (p.mode == FA_MODE_CHAINED) sched_chained(p.g, p.cg, root, &S);
+  else if (p.mode == FA_MODE_CHAINED) sched_chained(p.g, p.cg, root, weighted, &S);
   else sched_blocked(p.g, p.cg, p.bg, root, &S);
   return S.ops;
 }
@@ -728,7 +754,8 @@ int popc(unsigned v) { return __builtin_popcount(v); }
 // the vector columns, V elements); the scalar-column stacks and their
 // reductions are a few KB and cost only their launch.
 double kernel_bytes(const fa_xfer& x, int n_total, int64_t V, int es) {
-  const double b = (double)es * (double)(x.count > 0 ? x.count : V);
+  const double cols = (double)(x.count > 0 ? x.count : V);
+  const double b = (double)es * cols;
   switch (x.op) {
     case FA_X_K_SUM:
     case FA_X_K_STRIPE:
@@ -739,7 +766,10 @@ double kernel_bytes(const fa_xfer& x, int n_total, int64_t V, int es) {
     case FA_X_K_CHAIN: {
       const int lin = x.src == FA_B_STATE ? popc(fa_chain_levels(x.row0, n_total)) : 0;
       const int lout = x.dst == FA_B_STATE ? popc(fa_chain_levels(x.row0 + x.nrows, n_total)) : 1;
-      return (x.nrows + lin + std::max(lout, 1)) * b;
+      // (the state planes are fp32 whatever the clients hold; a finishing
+      // segment writes one row of the bucket's type)
+      const int out = x.dst == FA_B_STATE ? 4 * std::max(lout, 1) : es;
+      return (double)(x.nrows * es + 4 * lin + out) * cols;
     }
     case FA_X_K_COPY: return x.dst == FA_B_BLK ? 0.0 : 2 * b;
     case FA_X_K_DIV: return 2 * b;
@@ -749,11 +779,14 @@ double kernel_bytes(const fa_xfer& x, int n_total, int64_t V, int es) {
   }
 }
 
-// (es: bytes per element of the floating bucket, 2 in a 16-bit round)
+// (es: bytes per element of the floating bucket, 2 in a 16-bit round; the
+// cascade's state planes and the gathered weights are fp32 in every round)
 double elem_bytes(const fa_xfer& x, int es) {
   const int buf = x.op == FA_X_RECV ? x.dst : x.src;
   const int idx = x.op == FA_X_RECV ? x.dst_index : x.src_index;
-  return is_i64(buf, idx) ? 8.0 : (double)es;
+  if (is_i64(buf, idx)) return 8.0;
+  if (buf == FA_B_STATE || is_weights(buf, idx)) return 4.0;
+  return (double)es;
 }
 
 // A collective's bytes on each link direction of a rank (ring algorithms).
@@ -955,7 +988,19 @@ int all_schedules(const Geo& base, int mode, int nchunks, int xchg, int root, bo
 // The default entry's choice (fa_multi_select_layout): the exact form and
 // chunk count with the lowest modelled time; ties keep the earlier candidate
 // (blocked, then chained, then striped, fewer chunks first).
-int select_form(const Geo& base, unsigned mflags, int* mode, int* nchunks, double* us) {
+// A 16-bit bucket (base.elem): the striped form, and with `chain16` the
+// chained one — the same chunk counts, the same order of candidates.
+int select_form(const Geo& base, unsigned mflags, int* mode, int* nchunks, double* us,
+                bool chain16 = false) {
+  const bool h16 = base.elem != FA_ELEM_F32;
+  if (h16 && (mflags & FA_MULTI_REASSOCIATE))
+    return set_err(FA_E_INVAL, "fa_multi_select: the re-associated round runs on fp32 buckets");
+  if (h16 && base.nranks == 1) {
+    *mode = chain16 ? FA_MODE_CHAINED : FA_MODE_STRIPED;
+    *nchunks = 1;
+    if (us) *us = one_rank_cost(base).model_us;
+    return FA_OK;
+  }
   if (mflags & FA_MULTI_REASSOCIATE) {
     *mode = FA_MODE_SHARDED;
     *nchunks = 8;
@@ -977,9 +1022,10 @@ int select_form(const Geo& base, unsigned mflags, int* mode, int* nchunks, doubl
     int mode, nchunks;
   };
   std::vector<Cand> cand;
-  if (first_wide_block(base.nranks, base.counts.data(), nullptr, nullptr) < 0)
+  if (!h16 && first_wide_block(base.nranks, base.counts.data(), nullptr, nullptr) < 0)
     cand.push_back({FA_MODE_BLOCKED, 1});
-  for (int c : {4, 8, 16, 32}) cand.push_back({FA_MODE_CHAINED, c});
+  if (!h16 || chain16)
+    for (int c : {4, 8, 16, 32}) cand.push_back({FA_MODE_CHAINED, c});
   for (int c : {1, 2, 4, 8}) cand.push_back({FA_MODE_STRIPED, c});
   double best = 0.0;
   *mode = -1;
@@ -989,7 +1035,7 @@ int select_form(const Geo& base, unsigned mflags, int* mode, int* nchunks, doubl
     int rc = all_schedules(base, k.mode, k.nchunks, FA_XCHG_REDUCE, root, false, &sch, &V);
     if (rc) return rc;
     fa_round_cost c{};
-    if ((rc = model_schedules(sch, base.n_total, V, &c))) return rc;
+    if ((rc = model_schedules(sch, base.n_total, V, &c, elem_size(base.elem)))) return rc;
     if (*mode < 0 || c.model_us < best) {
       best = c.model_us;
       *mode = k.mode;
@@ -1012,12 +1058,13 @@ namespace {
 int describe_round(const char* who, int mode, int nranks, int rank, const int* counts,
                    const fa_seg* seg32, int nseg32, int64_t f32_numel, const fa_seg* seg64,
                    int nseg64, int64_t i64_numel, int nchunks, int exchange, unsigned flags,
-                   int root, int weighted, fa_xfer* ops, int cap, int* nops, int elem) {
+                   int root, int weighted, fa_xfer* ops, int cap, int* nops, int elem,
+                   unsigned ropts = 0) {
   if (!nops) return set_err(FA_E_INVAL, "%s: nops is NULL", who);
   *nops = 0;
   int rc = check_round_args(who, mode, &nchunks, exchange, root, nranks);
   if (rc) return rc;
-  if ((rc = check_round_elem(who, elem, mode, weighted))) return rc;
+  if ((rc = check_round_opts(who, elem, mode, weighted, ropts))) return rc;
   RoundGeo p;
   p.mode = mode;
   p.xchg = exchange;
@@ -1043,11 +1090,11 @@ int describe_round(const char* who, int mode, int nranks, int rank, const int* c
 int round_model(const char* who, int mode, int nranks, const int* counts, const fa_seg* seg32,
                 int nseg32, int64_t f32_numel, const fa_seg* seg64, int nseg64,
                 int64_t i64_numel, int nchunks, int exchange, unsigned flags, int root,
-                int weighted, fa_round_cost* out, int elem) {
+                int weighted, fa_round_cost* out, int elem, unsigned ropts = 0) {
   if (!out) return set_err(FA_E_INVAL, "%s: out is NULL", who);
   int rc = check_round_args(who, mode, &nchunks, exchange, root, nranks);
   if (rc) return rc;
-  if ((rc = check_round_elem(who, elem, mode, weighted))) return rc;
+  if ((rc = check_round_opts(who, elem, mode, weighted, ropts))) return rc;
   Geo g;
   rc = make_geo(nranks, 0, counts, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel, flags, who,
                 &g, elem);
@@ -1086,6 +1133,21 @@ int fa_describe_round_elem(int mode, int nranks, int rank, const int* counts,
                         i64_numel, nchunks, exchange, flags, root, weighted, ops, cap, nops, elem);
 }
 
+// (no option bit: the _elem entry exactly, its name in the messages included)
+int fa_describe_round_opts(int mode, int nranks, int rank, const int* counts, const fa_seg* seg32,
+                           int nseg32, int64_t f32_numel, const fa_seg* seg64, int nseg64,
+                           int64_t i64_numel, int nchunks, int exchange, unsigned flags, int root,
+                           int weighted, fa_xfer* ops, int cap, int* nops, int elem,
+                           unsigned ropts) {
+  if (!ropts)
+    return fa_describe_round_elem(mode, nranks, rank, counts, seg32, nseg32, f32_numel, seg64,
+                                  nseg64, i64_numel, nchunks, exchange, flags, root, weighted, ops,
+                                  cap, nops, elem);
+  return describe_round("fa_describe_round_opts", mode, nranks, rank, counts, seg32, nseg32,
+                        f32_numel, seg64, nseg64, i64_numel, nchunks, exchange, flags, root,
+                        weighted, ops, cap, nops, elem, ropts);
+}
+
 int fa_model_constants(double* link_gbps, double* hbm_gbps, double* group_us,
                        double* kernel_us) {
   const ModelConst& c = mc();
@@ -1113,6 +1175,17 @@ int fa_round_model_elem(int mode, int nranks, const int* counts, const fa_seg* s
                      flags, root, weighted, out, elem);
 }
 
+int fa_round_model_opts(int mode, int nranks, const int* counts, const fa_seg* seg32, int nseg32,
+                        int64_t f32_numel, const fa_seg* seg64, int nseg64, int64_t i64_numel,
+                        int nchunks, int exchange, unsigned flags, int root, int weighted,
+                        fa_round_cost* out, int elem, unsigned ropts) {
+  if (!ropts)
+    return fa_round_model_elem(mode, nranks, counts, seg32, nseg32, f32_numel, seg64, nseg64,
+                               i64_numel, nchunks, exchange, flags, root, weighted, out, elem);
+  return round_model("fa_round_model_opts", mode, nranks, counts, seg32, nseg32, f32_numel, seg64,
+                     nseg64, i64_numel, nchunks, exchange, flags, root, weighted, out, elem, ropts);
+}
+
 // The default multi-GPU entry's choice (fedcomm.hip fa_multi_plan_create):
 // select_form; e1 only on request (FA_MULTI_REASSOCIATE).
 int fa_multi_select_layout(int nranks, const int* counts, const fa_seg* seg32, int nseg32,
@@ -1130,6 +1203,35 @@ int fa_multi_select_layout(int nranks, const int* counts, const fa_seg* seg32, i
                           flags, "fa_multi_select", &g);
   if (rc) return rc;
   return select_form(g, mflags, mode, nchunks, model_us);
+}
+
+// ... on a bucket of `elem` elements.  FA_ELEM_F32 without an option: the
+// fp32 entry exactly.  16-bit: the striped form, or with FA_ROUND_CHAIN16 the
+// better of striped and chained.
+int fa_multi_select_layout_elem(int nranks, const int* counts, const fa_seg* seg32, int nseg32,
+                                int64_t f32_numel, const fa_seg* seg64, int nseg64,
+                                int64_t i64_numel, unsigned flags, unsigned mflags, int elem,
+                                unsigned ropts, int* mode, int* nchunks, double* model_us) {
+  if (elem == FA_ELEM_F32 && !ropts)
+    return fa_multi_select_layout(nranks, counts, seg32, nseg32, f32_numel, seg64, nseg64,
+                                  i64_numel, flags, mflags, mode, nchunks, model_us);
+  const char* who = "fa_multi_select_layout_elem";
+  if (!mode || !nchunks) return set_err(FA_E_INVAL, "%s: mode/nchunks is NULL", who);
+  *mode = -1;
+  *nchunks = 0;
+  if (nranks < 1 || !counts) return set_err(FA_E_INVAL, "%s: bad arguments", who);
+  if (mflags & ~(unsigned)(FA_MULTI_REASSOCIATE | FA_MULTI_ROOT_ALL))
+    return set_err(FA_E_INVAL, "%s: unknown flags 0x%x", who, mflags);
+  if (ropts & ~(unsigned)FA_ROUND_CHAIN16)
+    return set_err(FA_E_INVAL, "%s: unknown round options 0x%x", who, ropts);
+  if (elem == FA_ELEM_F32)
+    return set_err(FA_E_INVAL, "%s: FA_ROUND_CHAIN16 names the chained round on an fp16 / bf16 "
+                               "bucket (an fp32 bucket chains without it)", who);
+  Geo g;
+  const int rc = make_geo(nranks, 0, counts, seg32, nseg32, f32_numel, seg64, nseg64, i64_numel,
+                          flags, who, &g, elem);
+  if (rc) return rc;
+  return select_form(g, mflags, mode, nchunks, model_us, (ropts & FA_ROUND_CHAIN16) != 0);
 }
 
 int fa_multi_select(int nranks, const int* counts, unsigned mflags, int* mode) {

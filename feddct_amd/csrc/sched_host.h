@@ -98,6 +98,9 @@ int make_geo(int nranks, int rank, const int* counts, const fa_seg* seg32, int n
 // What a 16-bit round supports: the striped form, unweighted (`who` names the
 // entry in the message).  FA_ELEM_F32 passes everything.
 int check_round_elem(const char* who, int elem, int mode, int weighted);
+// ... with round options (fedagg_comm.h FA_ROUND_*): FA_ROUND_CHAIN16 admits
+// the chained round, mean or weighted, on a 16-bit bucket and nothing else.
+int check_round_opts(const char* who, int elem, int mode, int weighted, unsigned ropts);
 
 // The cut of r->g for r->mode.  The tile lists are what a plan's device side
 // is created from: chunk c = tiles [cut[c], cut[c + 1]) of g.t32 (e1, e2) or
@@ -116,6 +119,10 @@ inline bool is_comm(int op) { return op >= FA_X_SEND && op <= FA_X_BCAST; }
 // (buffer, index) holds int64 elements: the stacked / gathered int64 keys
 inline bool is_i64(int buf, int index) {
   return (buf == FA_B_STACK || buf == FA_B_GATHER) && index == 1;
+}
+// ... the ranks' fp32 weights (a weighted 16-bit chained round)
+inline bool is_weights(int buf, int index) {
+  return (buf == FA_B_STACK || buf == FA_B_GATHER) && index == 2;
 }
 bool on_comm_stream(const fa_xfer& x);
 bool reads_exchanged(const fa_xfer& x);

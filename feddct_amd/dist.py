@@ -31,8 +31,13 @@ round exists natively only).  The round forms:
   line reports it beside the time.
 
 On a native 16-bit layout (``BucketLayout(native16=True)``) the striped round
-is the only form: it runs on the fp16 / bf16 buckets themselves, unweighted
-(DESIGN §4.14); ``Aggregator`` takes it, the other two classes refuse.
+is the default form: it runs on the fp16 / bf16 buckets themselves, unweighted
+(DESIGN §4.14); ``Aggregator`` takes it, the other two classes refuse.  The
+chained round on 16-bit buckets is opt-in
+(``ChainAggregator(native16=True)``, ``Aggregator(chain16=True)``, DESIGN
+§4.15): the cascade state travels in fp32 planes, the clients stay 16-bit
+(fa_reduce_chain_elem), and it carries weights — the chain multiplies inside
+the kernel, so nothing pre-multiplied travels.
 
 int64 keys (a few bytes) always travel raw — an all-gather of every rank's
 int64 buckets — and are reduced exactly over all N_total clients.
@@ -98,17 +103,20 @@ def blocked_allowed(counts: Sequence[int]) -> bool:
 
 
 def exact_form(counts: Sequence[int], layout: Optional[BucketLayout] = None,
-               root_all: bool = False) -> str:
+               root_all: bool = False, chain16: bool = False) -> str:
     """The exact round the default entry takes for these shard counts: the
     form with the lowest modelled time (sched_host.cpp fa_multi_select_layout
     on ``layout``; None: fa_multi_select's nominal layout) — "blocked" (only
     where ``blocked_allowed``), "chained" or "striped".  ``root_all``: the
     result goes to every rank.  r05: "blocked" if allowed, else "chained".
-    A native 16-bit layout: always "striped" (the other forms move fp32 sums
-    or cascade state)."""
-    if layout is not None and layout.native16:
-        return "striped"   # the one exact form on fp16 / bf16 buckets
+    A native 16-bit layout: "striped" (the other forms move fp32 sums or
+    cascade state), unless ``chain16`` admits the chained round on 16-bit
+    buckets: then the model's pick of the two (fa_multi_select_layout_elem)."""
     from .comm import multi_select
+    if layout is not None and layout.native16:
+        if not chain16:
+            return "striped"   # the one exact form on fp16 / bf16 buckets by default
+        return multi_select(counts, layout=layout, root_all=root_all, chain16=True)
     return multi_select(counts, layout=layout, root_all=root_all)
 
 
@@ -614,16 +622,25 @@ def chain_levels(rows: int, n_total: int) -> int:
 
 
 class HipChainBackend(_HipI64):
-    """fa_reduce_chain over the vector-tile chunks; the raw scalar columns
-    (compact tail plan + int64 plan) reduced with fa_reduce."""
+    """fa_reduce_chain_elem over the vector-tile chunks; the raw scalar columns
+    (compact tail plan + int64 plan) reduced with fa_reduce.  ``elem``: the
+    floating bucket's element type (default: the layout's — FA_ELEM_F16 /
+    FA_ELEM_BF16 on a native 16-bit layout: 16-bit chunk plans, a 16-bit
+    compact tail plan, fp32 state planes)."""
 
-    def __init__(self, layout: BucketLayout, chunks, compact, tidx, t64):
+    def __init__(self, layout: BucketLayout, chunks, compact, tidx, t64, elem=None):
         from . import _lib
+        from .partition import layout_elem
         self._lib = _lib
         self.layout = layout
-        self.plans = [_lib.Plan(None, layout.f32_numel, None, 0, 0, tiles=t) for _, _, t in chunks]
+        if elem is None:
+            elem = layout_elem(layout)
+        self.elem = _lib.FA_ELEM_F32 if elem is None else int(elem)
+        pad = _lib.FA_PLAN_GAPS_ARE_PADDING
+        self.plans = [_lib.Plan.from_tiles(t, layout.f32_numel, 0, 0, pad, self.elem)
+                      for _, _, t in chunks]
         T = len(tidx)
-        self.plan_t32 = _lib.Plan(None, T, None, 0, 0, tiles=compact) if T else None
+        self.plan_t32 = _lib.Plan.from_tiles(compact, T, 0, 0, pad, self.elem) if T else None
         self.plan64 = (_lib.Plan(None, layout.f32_numel, None, layout.i64_numel, 0, tiles=t64)
                        if len(t64) else None)
         self.tout = None
@@ -633,20 +650,26 @@ class HipChainBackend(_HipI64):
         ch = L.FaChain(row0, n_total, state.data_ptr() if state_in else None,
                        None if out is not None else state.data_ptr(), plane)
         w = None if weights is None else (ctypes.c_float * len(weights))(*map(float, weights))
-        L.check(L.lib.fa_reduce_chain(self.plans[c].handle,
-                                      L.ptr_array([t.data_ptr() for t in clients32]),
-                                      len(clients32), w, ctypes.byref(ch),
-                                      out.data_ptr() if out is not None else None, 0,
-                                      self._stream()), "fa_reduce_chain")
+        L.check(L.lib.fa_reduce_chain_elem(self.plans[c].handle,
+                                           L.ptr_array([t.data_ptr() for t in clients32]),
+                                           len(clients32), w, ctypes.byref(ch),
+                                           out.data_ptr() if out is not None else None, 0,
+                                           self._stream()), "fa_reduce_chain_elem")
 
-    def tails(self, rows32, tidx, out32, weighted):
+    def tails(self, rows32, tidx, out32, weighted, weights=None):
+        """The gathered scalar columns into ``out32[tidx]``.  fp32 rows of a
+        weighted round arrive pre-multiplied (the ordered sum, no division);
+        16-bit rows arrive raw and ``weights`` holds every row's weight (a
+        16-bit plan has no FA_F_SUM_ONLY: the weighted reduce itself)."""
         L = self._lib
         if self.tout is None:
-            self.tout = torch.zeros(max(64, -(-len(tidx) // 64) * 64), device=out32.device)
+            self.tout = torch.zeros(max(64, -(-len(tidx) // 64) * 64), dtype=out32.dtype,
+                                    device=out32.device)
+        w = None if weights is None else (ctypes.c_float * len(weights))(*map(float, weights))
+        flags = L.FA_F_SUM_ONLY if weighted and weights is None else 0
         L.check(L.lib.fa_reduce(self.plan_t32.handle, L.ptr_array([r.data_ptr() for r in rows32]),
-                                None, len(rows32), None, self.tout.data_ptr(), None,
-                                L.FA_F_SUM_ONLY if weighted else 0, self._stream()),
-                "fa_reduce(tails)")
+                                None, len(rows32), w, self.tout.data_ptr(), None, flags,
+                                self._stream()), "fa_reduce(tails)")
         out32[tidx] = self.tout[:len(tidx)]
 
 
@@ -662,14 +685,26 @@ class ChainAggregator:
     travel — one float per element below 16 slots, two below 256.  The
     scalar columns (ILP-4 tails, M==1) and int64 keys are all-gathered raw and
     reduced by the result ranks.  ``final="reduce"``: the result on ``root``;
-    ``"allreduce"``: on every rank (a broadcast from the finisher)."""
+    ``"allreduce"``: on every rank (a broadcast from the finisher).
+
+    ``native16=True`` admits a native 16-bit layout (refused otherwise): the
+    clients, the result, the stacked scalar columns and the finisher's buffer
+    are fp16 / bf16, the state planes stay fp32 and travel as on fp32 buckets.
+    Weighted, the chain multiplies by the local weights inside the kernel, the
+    scalar columns are gathered raw and the ranks' weights beside them, and the
+    result ranks run the weighted reduce over the gathered rows."""
 
     def __init__(self, layout: BucketLayout, n_total: int, out32: torch.Tensor,
                  out64: torch.Tensor, group=None, backend=None, final: str = "reduce",
-                 root: int = 0, nchunks: int = 16, counts: Optional[Sequence[int]] = None):
+                 root: int = 0, nchunks: int = 16, counts: Optional[Sequence[int]] = None,
+                 native16: bool = False):
         from .partition import chain_cut
         check_final(final)
-        refuse_native16(layout, "ChainAggregator")
+        if not native16:
+            refuse_native16(layout, "ChainAggregator")
+        if layout.native16 and out32.dtype != layout.float_dtype:
+            raise TypeError(f"ChainAggregator: a {out32.dtype} result bucket on a "
+                            f"{layout.float_dtype} layout")
         self.layout, self.n_total = layout, n_total
         self.out32, self.out64 = out32, out64
         self.group = group
@@ -697,9 +732,13 @@ class ChainAggregator:
                     and self.root != me else None)
         nmax = max(self.counts)
         self.nmax = nmax
-        self.stack32 = torch.zeros((nmax, max(self.trow, 1)), dtype=torch.float32, device=dev)
-        self.gather32 = torch.zeros((self.world * nmax, max(self.trow, 1)), dtype=torch.float32,
-                                    device=dev)
+        # (the layout's dtype: fp32, or the raw 16-bit rows of a native 16-bit layout)
+        self.stack32 = torch.zeros((nmax, max(self.trow, 1)), dtype=layout.float_dtype, device=dev)
+        self.gather32 = torch.zeros((self.world * nmax, max(self.trow, 1)),
+                                    dtype=layout.float_dtype, device=dev)
+        # a weighted 16-bit round: the ranks' weights, padded to nmax
+        self.wstack = torch.zeros(nmax, dtype=torch.float32, device=dev)
+        self.wgather = torch.zeros(self.world * nmax, dtype=torch.float32, device=dev)
         w64 = max(1, layout.i64_numel)
         self.stack64 = torch.zeros((nmax, w64), dtype=torch.int64, device=dev)
         self.gather64 = torch.zeros((self.world * nmax, w64), dtype=torch.int64, device=dev)
@@ -717,12 +756,17 @@ class ChainAggregator:
         me, F = self.rank, self.finisher
         n_loc = self.counts[me]
         assert len(local32) == n_loc
+        h16 = self.layout.native16
+        for t in local32:   # before any exchange, so every rank refuses alike
+            if h16 and t.dtype != self.layout.float_dtype:
+                raise TypeError(f"ChainAggregator: a {t.dtype} bucket on a native "
+                                f"{self.layout.float_dtype} layout")
         result = self.root < 0 or self.root == me
         # the raw scalar columns: stacked, gathered while the chain runs
         if self.T:
             for j, t in enumerate(local32):
                 v = t[self.tidx]
-                if weights is not None:
+                if weights is not None and not h16:
                     # a Python scalar, not a device tensor made from one: that
                     # is a blocking upload, one stream synchronisation per client
                     # (the product is the same fp32 multiply by the fp32 weight)
@@ -736,6 +780,13 @@ class ChainAggregator:
                                                   async_op=True))
         if self.layout.i64_numel:
             gw.append(dist.all_gather_into_tensor(self.gather64, self.stack64, group=self.group,
+                                                  async_op=True))
+        wgather = h16 and weights is not None and self.T
+        if wgather:   # 16-bit rows travel raw: the result ranks need every weight
+            self.wstack.zero_()
+            if n_loc:
+                self.wstack[:n_loc] = torch.from_numpy(np.asarray(weights, np.float32))
+            gw.append(dist.all_gather_into_tensor(self.wgather, self.wstack, group=self.group,
                                                   async_op=True))
         for w in gw:   # (gloo runs collectives and P2P on one thread: finish first)
             w.wait()
@@ -773,8 +824,9 @@ class ChainAggregator:
                     p2p([(dist.irecv, self.out32[lo:hi], self._peer(F))], self.group)
         if result:
             if self.T:
+                wall = self.wgather.cpu().numpy()[self.rows] if wgather else None
                 self.backend.tails([self.gather32[r] for r in self.rows], self.tidx, self.out32,
-                                   weights is not None)
+                                   weights is not None, *(() if wall is None else (wall,)))
             self.backend.reduce_i64([self.gather64[r] for r in self.rows], self.out64)
 
 
@@ -805,7 +857,12 @@ class Aggregator:
     ``final="reduce"`` puts the result on ``root`` (default: the last rank
     holding slots, where the chained round ends); ``"allreduce"`` on every
     rank.  ``weights``: this rank's fp32 client weights (exact rounds only).
-    ``self.form`` names what runs, e.g. "blocked/native"."""
+    ``self.form`` names what runs, e.g. "blocked/native".
+
+    ``chain16=True`` (a native 16-bit layout): the chained round on 16-bit
+    buckets joins the candidates — the form ``exact_form(..., chain16=True)``
+    picks, and with ``weights`` the chained form (the striped 16-bit round
+    still refuses weights)."""
 
     def __init__(self, layout: BucketLayout, local32: List[torch.Tensor],
                  local64: List[torch.Tensor], n_total: int, out32: torch.Tensor,
@@ -813,7 +870,7 @@ class Aggregator:
                  root: Optional[int] = None, weights: Optional[Sequence[float]] = None,
                  counts: Optional[Sequence[int]] = None, exact: bool = True,
                  native: Optional[bool] = None, backend=None, nchunks: Optional[int] = None,
-                 stripe_backend=None):
+                 stripe_backend=None, chain16: bool = False):
         check_final(final)
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         if counts is None:
@@ -837,10 +894,17 @@ class Aggregator:
             self.form = "e1/torch.distributed"
             self._step = self._agg.step
             return
-        if layout.native16 and exact and weights is not None:
+        chain16 = bool(chain16) and layout.native16
+        if layout.native16 and exact and weights is not None and not chain16:
             raise ValueError("Aggregator: weighted rounds on 16-bit buckets are not built (the "
                              "pre-multiplied rows are fp32 values)")
-        if layout.native16 and backend is not None and stripe_backend is None:
+
+        def form():
+            if chain16 and weights is not None:
+                return "chained"   # the one 16-bit round that carries weights
+            return exact_form(counts, layout, root_all=final != "reduce", chain16=chain16)
+        if layout.native16 and backend is not None and stripe_backend is None \
+                and not (chain16 and form() == "chained"):
             # (the fp32 path keeps its behaviour: there the model may still pick
             # the chained form, which ``backend`` serves)
             raise ValueError("Aggregator: a native 16-bit layout runs the striped round, whose "
@@ -858,7 +922,7 @@ class Aggregator:
                                          counts=counts, nchunks=nchunks or 0)
             self.form = f"{self._agg.mode}/native"
             self._step = self._agg.step
-        elif exact_form(counts, layout, root_all=final != "reduce") == "striped":
+        elif form() == "striped":
             self._agg = StripedAggregator(layout, n_total, out32, out64, group=group,
                                           backend=stripe_backend, final=final, root=root,
                                           nchunks=nchunks or 4, counts=counts)
@@ -867,7 +931,7 @@ class Aggregator:
         else:
             self._agg = ChainAggregator(layout, n_total, out32, out64, group=group,
                                         backend=backend, final=final, root=root,
-                                        nchunks=nchunks or 16, counts=counts)
+                                        nchunks=nchunks or 16, counts=counts, native16=chain16)
             self.form = "chained/torch.distributed"
             self._step = lambda: self._agg.step(self.local32, self.local64, self.weights)
 

@@ -150,7 +150,7 @@ def chain_cut(layout: BucketLayout, nchunks: int):
     t32 = t32[np.argsort(t32[:, 0], kind="stable")]
     vec = t32[t32[:, 2] == 0]
     sc = t32[t32[:, 2] != 0]
-    ci = cut_index(vec, nchunks)
+    ci = cut_index(vec, nchunks, align=cut_align(layout))
     chunks = []
     for g in range(nchunks):
         if ci[g] == ci[g + 1]:

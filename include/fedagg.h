@@ -235,7 +235,8 @@ int fa_plan_create_from_tiles(const fa_tile_desc *tiles, int ntiles,
  *   bucket, or on a mixed plan the fp32 one of f32_numel floats).  A subset
  *   does not cover its bucket, so FA_F_BCAST and FA_F_BCAST_ONLY are refused
  *   with nothing written (the coverage rule above), as are FA_F_SUM_ONLY and
- *   fa_reduce_chain.
+ *   fa_reduce_chain (a subset of vector tiles chains through
+ *   fa_reduce_chain_elem).
  * Every other pair is FA_E_INVAL.  *out is cleared first. */
 int fa_plan_create_from_tiles_elem(const fa_tile_desc *tiles, int ntiles,
                                    int64_t f32_numel, int64_t i64_numel,
@@ -437,6 +438,24 @@ unsigned fa_chain_levels(int rows, int n_total);
 int fa_reduce_chain(const fa_plan *plan, const float *const *c32, int n,
                     const float *weights, const fa_chain *chain, float *out32,
                     unsigned flags, void *stream);
+/* fa_reduce_chain for a plan of any element type.
+ *   fp32 plan : fa_reduce_chain exactly (its checks, its messages, its bits).
+ *   16-bit plan of vector tiles only (fa_plan_create_from_tiles_elem, elem
+ *     FA_ELEM_F16 / FA_ELEM_BF16, torch's CPU order): c[i] are the clients'
+ *     16-bit buckets.  The state planes stay fp32 — element e of level l at
+ *     state + l*plane + e, plane >= the plan's f32_numel in elements and a
+ *     multiple of 4 — and fa_chain_levels is unchanged.  A segment that does
+ *     not finish stores the planes its levels name and nothing else; the last
+ *     one sums the levels, divides by n_total unless weighted, and rounds once
+ *     to nearest-even into the 16-bit bucket `out` (a mixed plan, out_elem
+ *     FA_ELEM_F32: the unrounded fp32 value into the fp32 bucket `out`).
+ *     Segments chained in slot order give one 16-bit fa_reduce's bits.
+ *   Refused with nothing written: a torch-GPU-order plan, a plan with scalar
+ *     or int64 tiles, FA_F_SUM_ONLY on a 16-bit result, a state or out buffer
+ *     that is not 16-B aligned, a NULL or misaligned client. */
+int fa_reduce_chain_elem(const fa_plan *plan, const void *const *c, int n,
+                         const float *weights, const fa_chain *chain,
+                         void *out, unsigned flags, void *stream);
 
 /* Stateless fp32 mean over segments (plan cached internally by layout). */
 int fa_mean_f32(const float *const *clients, int n, int64_t numel, float *out,

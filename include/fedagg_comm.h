@@ -396,6 +396,25 @@ int fa_describe_round_elem(int mode, int nranks, int rank, const int *counts,
                            int weighted, fa_xfer *ops, int cap, int *nops,
                            int elem);
 
+/* ... with round options.  ropts == 0: fa_describe_round_elem exactly.
+ * FA_ROUND_CHAIN16 with a 16-bit `elem` and FA_MODE_CHAINED: the chained round
+ * on the 16-bit geometry (vector chunks cut on 128-element boundaries).
+ * CLIENT / OUT / FIN and the stacked scalar columns (STACK / GATHER index 0)
+ * hold 16-bit elements; the STATE planes stay fp32 (fedagg.h
+ * fa_reduce_chain_elem).  weighted != 0 is allowed: the chain kernels multiply
+ * by the local weights, the scalar columns travel raw, and the ranks' fp32
+ * weights are all-gathered beside them (STACK / GATHER index 2, nmax floats
+ * per rank) for the result ranks' weighted reduce; there is no K_SCALE pass.
+ * The bit with another mode or with FA_ELEM_F32, and any other bit, is
+ * FA_E_INVAL with the reason.  Host only: dist.py runs the round. */
+#define FA_ROUND_CHAIN16 1u
+int fa_describe_round_opts(int mode, int nranks, int rank, const int *counts,
+                           const fa_seg *seg32, int nseg32, int64_t f32_numel,
+                           const fa_seg *seg64, int nseg64, int64_t i64_numel,
+                           int nchunks, int exchange, unsigned flags, int root,
+                           int weighted, fa_xfer *ops, int cap, int *nops,
+                           int elem, unsigned ropts);
+
 /* ---- the round cost model (r06), host only ---------------------------------
  * Every rank's schedule (fa_describe_round) timed by a discrete-event replay
  * of the executor's rules: per rank a communication stream and the caller's
@@ -456,6 +475,29 @@ int fa_round_model_elem(int mode, int nranks, const int *counts,
                         const fa_seg *seg64, int nseg64, int64_t i64_numel,
                         int nchunks, int exchange, unsigned flags, int root,
                         int weighted, fa_round_cost *out, int elem);
+
+/* ... with round options (fa_describe_round_opts; ropts == 0:
+ * fa_round_model_elem exactly).  A 16-bit chained round counts 2 bytes per
+ * element of CLIENT / OUT / FIN / STACK / GATHER traffic and 4 per element of
+ * a STATE plane, in the kernels' HBM bytes and on the links. */
+int fa_round_model_opts(int mode, int nranks, const int *counts,
+                        const fa_seg *seg32, int nseg32, int64_t f32_numel,
+                        const fa_seg *seg64, int nseg64, int64_t i64_numel,
+                        int nchunks, int exchange, unsigned flags, int root,
+                        int weighted, fa_round_cost *out, int elem,
+                        unsigned ropts);
+/* fa_multi_select_layout on a bucket of `elem` elements.  FA_ELEM_F32 with
+ * ropts == 0: the fp32 entry exactly.  A 16-bit elem: the striped form (the
+ * one exact 16-bit round without an option), or with FA_ROUND_CHAIN16 the
+ * lower modelled time of the chained and striped candidates — the fp32
+ * entry's chunk counts, order and tie-break.  FA_MULTI_REASSOCIATE on a
+ * 16-bit elem, the bit with FA_ELEM_F32, and any other bit are FA_E_INVAL. */
+int fa_multi_select_layout_elem(int nranks, const int *counts,
+                                const fa_seg *seg32, int nseg32,
+                                int64_t f32_numel, const fa_seg *seg64,
+                                int nseg64, int64_t i64_numel, unsigned flags,
+                                unsigned mflags, int elem, unsigned ropts,
+                                int *mode, int *nchunks, double *model_us);
 
 #ifdef __cplusplus
 }
